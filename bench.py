@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the MI355X Ed25519-verify / SHA-512-digest hot path.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...     (one process per GPU, RCCL)
 
 Headline (BASELINE.json metric): Ed25519 verifies/s.  Workload = BASELINE config 2:
@@ -11,6 +11,12 @@ distinct keys; no data-path collective).  A "step" is one verification pass over
 triples with inputs resident in HBM.  The per-shard verdict bitmaps are all-gathered over
 RCCL after the timed region and the gather is timed separately (it is not needed for
 correctness: every rank already holds its verdicts).
+
+A plain run does the headline alone: set-up, warm-up, the K timed steps, the result line (metric,
+value, unit, ms_per_step = wall milliseconds per timed step, ...).  --dump-outputs DIR writes the
+verdicts the last timed step produced (bit i of the verdict words as element i) to DIR/verdicts.npy
+(float32; per rank at N > 1); the inputs are derived from fixed labels, so two builds given the same
+arguments verify the same triples.  Everything below runs with --full only, after the headline.
 
 Secondary leg (same JSON line, "digest"): BASELINE config 4, SHA-512[..32] of 100,000
 worker batches of 508,052 B (977 x 512-B txs, bincode WorkerMessage::Batch), hashed from a
@@ -1224,6 +1230,22 @@ def bench_cfg2_host_abi(lib, msgs, pks, sigs, reps: int):
             "verifies_per_s": n / med, "ms_per_call": med * 1e3, "reps": reps, "verdicts_ok": ok}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path: str, arrays: dict, writers: int = 1) -> None:
+    """--dump-outputs: each array as path/<name>.npy in float32 (verdict bits are exact in it), so that
+    two builds can be compared output for output.  The files of all `writers` (ranks) together stay within
+    DUMP_MAX_BYTES: a larger array is cut to a fixed sample of its elements (seeded, sorted indices)."""
+    os.makedirs(path, exist_ok=True)
+    cap = DUMP_MAX_BYTES // 4 // max(1, len(arrays) * writers)
+    for name, a in arrays.items():
+        a = np.asarray(a).reshape(-1)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(0x4E57).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a.astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1245,6 +1267,12 @@ def main():
                     help="seconds of back-to-back launches before the stamped clock launch (0 = skip)")
     ap.add_argument("--e2e-reps", type=int, default=3,
                     help="cfg 2 end to end through the host ABI from pageable host buffers (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the in-kernel clock, the reject check, the digest "
+                         "leg, configs 1/3/4/5, the CPU baselines and the roofline entries (the options above size "
+                         "or skip those legs; without --full none of them runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32)")
     args = ap.parse_args()
 
     import torch
@@ -1271,7 +1299,10 @@ def main():
         e1.record()
     barrier(world)
     dt = max_over_ranks(time.perf_counter() - t0, world)
-    ok = bool(device.unpack_bits(words, n).all())
+    verdicts = device.unpack_bits(words, n)   # what the last timed step left in `words`
+    ok = bool(verdicts.all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"verdicts" if world == 1 else "verdicts_rank%d" % rank: verdicts}, world)
     kernel_ms = sum(e0.elapsed_time(e1) for e0, e1 in evs) / len(evs)
     # verdict all-gather over RCCL (not needed for correctness; timed separately)
     gather_ms = None
@@ -1286,6 +1317,27 @@ def main():
         ok = ok and bool(device.unpack_bits(allw, world * words.numel() * 64).all())
     value = world * n * args.steps / dt
     effective_tops = n / (kernel_ms * 1e-3) * ops_per_verify() / 1e12
+    line = {
+        "metric": METRIC, "value": value, "unit": "verifies/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "int64",
+        "data": "synthetic: SHA-512-derived seeds/messages, RFC 8032 keygen+sign on the GPU (SURVEY.md §8(d) cfg 2)",
+        "config": {"workload": "cfg2: %d independent (32-B msg, pk, sig) triples per GPU, all valid, "
+                               "verify_strict" % n,
+                   "global_batch": world * n, "parallelism": "shard%d" % world,
+                   "verdicts_ok": ok, "verdict_allgather_ms": gather_ms, "allgather_needed": False},
+        # the hash of the sources libnwc.so was compiled from (narwhal_amd/build.py source_id)
+        "build_id": lib.nwc_build_id().decode(),
+    }
+    if not args.full:
+        # a plain run ends here: the headline alone (every other leg, check and baseline: --full)
+        if rank == 0:
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            import torch.distributed as dist
+            dist.destroy_process_group()
+        return
+
     # the clock the chip held under this load (MI355X_MICROARCH.md DVFS item 6): ~2 s more of
     # back-to-back launches, then one launch of the kernel's stamp build (never the timed kernel)
     clock = None
@@ -1389,24 +1441,9 @@ def main():
             digest["valu_frac_issue"] = digest["valu_frac"] * dcyc / 2
         digest["pmc_source"] = dpc["source"]
     if rank == 0:
-        line = {
-            "metric": METRIC, "value": value, "unit": "verifies/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "int64",
-            "data": "synthetic: SHA-512-derived seeds/messages, RFC 8032 keygen+sign on the GPU (SURVEY.md §8(d) cfg 2)",
-            "config": {"workload": "cfg2: %d independent (32-B msg, pk, sig) triples per GPU, all valid, "
-                                   "verify_strict" % n,
-                       "global_batch": world * n, "parallelism": "shard%d" % world,
-                       "verdicts_ok": ok, "reject_check": reject, "verdict_allgather_ms": gather_ms,
-                       "allgather_needed": False},
-            "roofline": roofline_verify(vpc, n, kernel_ms, effective_tops, clock),
-            "cpu_baseline": cpu,
-            "digest": digest,
-            "configs": extras,
-            # the hash of the sources libnwc.so was compiled from (narwhal_amd/build.py source_id)
-            "build_id": lib.nwc_build_id().decode(),
-            "memory": _lib.memory_info(),
-        }
+        line["config"]["reject_check"] = reject
+        line.update({"roofline": roofline_verify(vpc, n, kernel_ms, effective_tops, clock), "cpu_baseline": cpu,
+                     "digest": digest, "configs": extras, "memory": _lib.memory_info()})
         print(json.dumps(line), flush=True)
     if world > 1:
         import torch.distributed as dist

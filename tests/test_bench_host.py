@@ -22,6 +22,23 @@ def test_cfg4_pool_host_matches_the_bytewise_recipe():
     assert d == hashlib.sha512(bench.cfg4_host_batch(7)).digest()[:32]
 
 
+def test_dump_outputs_writes_float32_within_the_cap(tmp_path, monkeypatch):
+    """--dump-outputs: every array as <name>.npy in float32, bits exact; an array above the byte cap
+    is cut to the same seeded sample on every call (so two builds' dumps compare element for element)."""
+    import bench
+    bits = np.random.default_rng(5).random(3001) < 0.9
+    bench.dump_outputs(str(tmp_path / "a"), {"verdicts": bits})
+    got = np.load(tmp_path / "a" / "verdicts.npy")
+    assert got.dtype == np.float32 and got.shape == (3001,) and (got == bits).all()
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 1000)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"verdicts": bits, "other": np.arange(3001)}, writers=2)
+    b, c = (np.load(tmp_path / d / "other.npy") for d in ("b", "c"))
+    assert b.dtype == np.float32 and b.shape == (250,) and (b == c).all() and (np.diff(b) > 0).all()
+    assert np.load(tmp_path / "b" / "verdicts.npy").shape == (250,)
+    assert (np.load(tmp_path / "b" / "verdicts.npy") == bits[b.astype(int)]).all()
+
+
 def test_cert_shards_balance_votes_and_keep_certificates_whole():
     """bench's config-3 sharding at world > 1: whole certificates per rank, balanced by votes."""
     import bench

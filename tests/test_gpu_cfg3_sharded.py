@@ -23,7 +23,7 @@ def test_cfg3_sharded_gloo(world):
     env = dict(os.environ, NWC_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", str(world), "--steps", "2", "--warmup", "1", "--triples", "65536", "--digest-batches", "0",
+           "--gpus", str(world), "--full", "--steps", "2", "--warmup", "1", "--triples", "65536", "--digest-batches", "0",
            "--cpu-budget", "0", "--cfg3-certs", str(certs), "--cfg1-calls", "0", "--wire-certs", "0",
            "--cfg5-total", "0", "--clock-s", "0"]
     r = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=240 + 40 * world)

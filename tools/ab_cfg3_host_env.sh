@@ -6,7 +6,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUNDS=$1; shift
 mkdir -p $R/gpurun_out
-ARGS="--steps 2 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --triples 64 --clock-s 0 --digest-batches 0 --cfg5-total 0 --e2e-reps 0 --wire-certs 0 --host-digest-group 0"
+ARGS="--full --steps 2 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --triples 64 --clock-s 0 --digest-batches 0 --cfg5-total 0 --e2e-reps 0 --wire-certs 0 --host-digest-group 0"
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
     name=${v%%:*}; envs=${v#*:}

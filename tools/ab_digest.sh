@@ -5,7 +5,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUNDS=$1; shift
 mkdir -p $R/gpurun_out
-ARGS="--steps 2 --warmup 1 --triples 65536 --cpu-budget 0 --cfg1-calls 0 --cfg3-certs 0 --wire-certs 0 --cfg5-total 0 --e2e-reps 0 --digest-steps 3"
+ARGS="--full --steps 2 --warmup 1 --triples 65536 --cpu-budget 0 --cfg1-calls 0 --cfg3-certs 0 --wire-certs 0 --cfg5-total 0 --e2e-reps 0 --digest-steps 3"
 for r in $(seq 1 $ROUNDS); do
   for lib in "$@"; do
     NWC_LIB_PATH=$R/$lib timeout -k 10 240 python3 $R/bench.py $ARGS > $R/gpurun_out/abd_last.json 2> $R/gpurun_out/abd_last.err

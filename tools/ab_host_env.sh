@@ -6,7 +6,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUNDS=$1; VAR=$2; A=$3; B=$4
 mkdir -p $R/gpurun_out
-ARGS="--steps 2 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --wire-certs 0 --cfg5-total 0 --digest-batches 0 --host-digest-group 0 --e2e-reps 3"
+ARGS="--full --steps 2 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --wire-certs 0 --cfg5-total 0 --digest-batches 0 --host-digest-group 0 --e2e-reps 3"
 for r in $(seq 1 $ROUNDS); do
   for v in $A $B; do
     env $VAR=$v timeout -k 10 300 python3 $R/bench.py $ARGS > $R/gpurun_out/abe_last.json 2> $R/gpurun_out/abe_last.err

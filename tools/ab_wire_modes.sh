@@ -6,7 +6,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 ROUNDS=$1; shift
 mkdir -p $R/gpurun_out
-ARGS="--steps 6 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --cfg3-certs 0 --triples 65536 --digest-batches 0 --cfg5-total 0 --e2e-reps 0 --host-digest-group 0 --clock-s 0"
+ARGS="--full --steps 6 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --cfg3-certs 0 --triples 65536 --digest-batches 0 --cfg5-total 0 --e2e-reps 0 --host-digest-group 0 --clock-s 0"
 for r in $(seq 1 $ROUNDS); do
   for v in "$@"; do
     env ${v//,/ } timeout -k 10 300 python3 $R/bench.py $ARGS > $R/gpurun_out/abm_last.json 2> $R/gpurun_out/abm_last.err

@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/msm_phases
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export NWC_BENCH_CFG3_LEGS=clean_no_cache_msm NWC_MSM_ADAPT=0
-ARGS="--steps 4 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --triples 65536 --digest-batches 0 --cfg5-total 0 --e2e-reps 0 --wire-certs 0 --clock-s 0 --host-digest-group 0"
+ARGS="--full --steps 4 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --triples 65536 --digest-batches 0 --cfg5-total 0 --e2e-reps 0 --wire-certs 0 --clock-s 0 --host-digest-group 0"
 ROUNDS=${1:-2}; shift || true
 LIBS=${@:-narwhal_amd/libnwc.so narwhal_amd/variants/msm_cut1.so narwhal_amd/variants/msm_cut2.so}
 for r in $(seq 1 $ROUNDS); do

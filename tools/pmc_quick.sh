@@ -1,6 +1,7 @@
 #!/bin/bash
 # Quick counter passes for one bench configuration (development aid; the round's committed
 # evidence comes from tools/profile_round.sh).  Usage: tools/pmc_quick.sh TAG "<bench args>"
+# (with --full among them for any leg beside the headline)
 set -e
 TAG=$1
 ARGS=$2

@@ -29,22 +29,22 @@ run_tag() {
 want() { [ $# -eq 0 ] || [[ " $ONLY " == *" $1 "* ]]; }
 ONLY="$*"
 if [ -z "$ONLY" ] || want head; then
-  run_tag head --steps 5 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --cfg3-certs 0 --wire-certs 0 --cfg5-total 0 --e2e-reps 0 --clock-s 0
+  run_tag head --full --steps 5 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --cfg3-certs 0 --wire-certs 0 --cfg5-total 0 --e2e-reps 0 --clock-s 0
 fi
 if [ -z "$ONLY" ] || want c3lk; then
   export NWC_BENCH_CFG3_LEGS=launch_keys
-  run_tag c3lk --steps 8 --warmup 1 $SMALL --cfg5-total 0 --cfg3-certs 100000
+  run_tag c3lk --full --steps 8 --warmup 1 $SMALL --cfg5-total 0 --cfg3-certs 100000
 fi
 if [ -z "$ONLY" ] || want c3dk; then
   export NWC_BENCH_CFG3_LEGS=dalek_launch_keys
-  run_tag c3dk --steps 8 --warmup 1 $SMALL --cfg5-total 0 --cfg3-certs 100000
+  run_tag c3dk --full --steps 8 --warmup 1 $SMALL --cfg5-total 0 --cfg3-certs 100000
 fi
 if [ -z "$ONLY" ] || want c3msm; then
   export NWC_BENCH_CFG3_LEGS=clean_no_cache_msm
-  run_tag c3msm --steps 8 --warmup 1 $SMALL --cfg5-total 0 --cfg3-certs 100000
+  run_tag c3msm --full --steps 8 --warmup 1 $SMALL --cfg5-total 0 --cfg3-certs 100000
 fi
 unset NWC_BENCH_CFG3_LEGS
 if [ -z "$ONLY" ] || want c5; then
-  run_tag c5 --steps 2 --warmup 1 $SMALL --cfg3-certs 0 --cfg5-total 67108864
+  run_tag c5 --full --steps 2 --warmup 1 $SMALL --cfg3-certs 0 --cfg5-total 67108864
 fi
 echo done

@@ -6,7 +6,7 @@ set -e
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/straus_ab
 mkdir -p $OUT
-ARGS="--steps 3 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --triples 65536 --digest-batches 0 --cfg5-total 0 --wire-certs 0 --e2e-reps 0 --cfg3-certs ${CFG3_CERTS:-100000}"
+ARGS="--full --steps 3 --warmup 1 --cpu-budget 0 --cfg1-calls 0 --triples 65536 --digest-batches 0 --cfg5-total 0 --wire-certs 0 --e2e-reps 0 --cfg3-certs ${CFG3_CERTS:-100000}"
 for nq in ${1:-4 8 12 16}; do
   NWC_STRAUS_NQ=$nq timeout -k 10 300 python3 $R/bench.py $ARGS > $OUT/bench_nq$nq.json 2> $OUT/bench_nq$nq.err
   python3 - $OUT/bench_nq$nq.json $nq <<'EOF'
