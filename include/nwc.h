@@ -41,6 +41,9 @@ int nwc_init(uint32_t device_mask);
 void nwc_shutdown(void);
 /* Text of the last error on the calling thread ("" if none). */
 const char* nwc_last_error(void);
+/* Code (< 0) of the last error on the calling thread (0 if none): what an entry that returns a
+ * pointer, such as nwc_signer_create, would have returned as an int. */
+int nwc_last_error_code(void);
 /* ABI version (major << 16 | minor). */
 int nwc_version(void);
 /* Number of devices initialised. */
@@ -53,7 +56,9 @@ const char* nwc_build_id(void);
 /* ---- device memory (a primary and a worker may share one GPU) ------------------------ */
 /* Bytes held by this process on the calling thread's device (nwc_dev_set_device): tables =
  * basepoint tables (radix-2^24 ladder tables 2.1 GB, radix-2^22 comb 3.2 GB unless NWC_COMB16=0,
- * small ones), built by the first call that verifies or signs -- 0 in a process that only digests;
+ * small ones), built by the first call that verifies (or generates a workload with
+ * nwc_dev_keygen_sign) -- 0 in a process that only digests; a signer (nwc_signer_create) adds only
+ * its own 60-KB basepoint table, so a process that only signs reports less than 1 MiB here;
  * committee = the nwc_set_committee cache (20 MB per key with combs); auto_cache = the auto key
  * cache (NWC_AUTO_KEYS) and the launch keys (20 MB of comb per key that joined); scratch =
  * per-launch buffers grown on demand (ladder tables, Straus tables, MSM groups, staging, message
@@ -77,7 +82,9 @@ int nwc_trim(void);
  * "msm_adapt" = 0 / 1 (default 1, env NWC_MSM_ADAPT): the MSM entry's skip policy (0 = the
  * equation on every group); "dalek_seed" = a fixed 32-bit seed of the batch entries' random z_i
  * (z_i = SHA-512(seed as 4 LE bytes || 28 zero bytes || u64le(i))[..16]; 0, the default = 32 bytes
- * of the host CSPRNG per launch), so tests can compute dalek's equation for the same z_i.
+ * of the host CSPRNG per launch), so tests can compute dalek's equation for the same z_i;
+ * "sign_path" = the signers' kernel: 0 (default) by size (NWC_SIGN_WIDE_MAX), 1 = the
+ * signature-per-lane kernel, 2 = the wave-per-signature kernel, at any n.
  * NWC_ERR_ARG for an unknown name or value.
  * Not part of the crate's API. */
 int nwc_diag_set(const char* name, int64_t value);
@@ -140,6 +147,53 @@ int nwc_verify_batch_straus_many(const uint8_t* digests, const uint32_t* offsets
 int nwc_verify_batch_msm_many(const uint8_t* digests, const uint32_t* offsets, const uint8_t* pks,
                               const uint8_t* sigs, size_t m, uint8_t* cert_ok_bitmap,
                               uint8_t* bad_vote_bitmap);
+
+/* ---- signing with a registered key ------------------------------------------------------- */
+/* crypto::Signature::new, SignatureService and generate_keypair (crypto/src/lib.rs:163-191,
+ * 222-250; called for every header and vote: primary/src/messages.rs:24-46, 115-129).  A signer
+ * is an opaque handle (void*) that owns the expanded key -- a = clamp(h[..32]) mod l, prefix =
+ * h[32..] and A = aB for h = SHA-512(seed) -- in memory of the calling thread's device
+ * (nwc_dev_set_device), computed once by create; the host side keeps the public half only, and the
+ * pinned stage the seed crossed is zeroed before create returns.  Signatures are RFC 8032 /
+ * dalek Keypair::sign over the 32 digest bytes: deterministic, byte-identical to dalek's.
+ *
+ * Deliberate deviation from ed25519-dalek 1.0.1: its Keypair::from_bytes does not check that
+ * secret64[32..64] is the public key of the seed and then signs with whatever public half it was
+ * given -- a signature that fails verification and, next to one made with the right half, gives
+ * the key away.  nwc_signer_create derives A and refuses a secret whose public half differs
+ * (NULL, nwc_last_error_code = NWC_ERR_ARG).
+ *
+ * The sign kernels read no memory address, take no branch and bound no loop by the key, the nonce
+ * or their digits (DESIGN.md "Signing"); kernel arguments carry a pointer to the key record, never
+ * key bytes.  Signing builds none of the verification tables: a signer uses a 60-KB basepoint table
+ * of its own, built on the device by the first create.
+ *
+ * Conventions as everywhere here: thread-safe (calls on one signer are serialised on its device),
+ * errors < 0, NWC_ERR_ARG for null pointers, NWC_ERR_NOT_INIT before nwc_init, n == 0 is a no-op
+ * returning 0.  n <= NWC_SIGN_WIDE_MAX (environment, default 256, measured: DESIGN.md "Signing") takes the
+ * wave-per-signature kernel, larger calls the signature-per-lane kernel; host calls stage their
+ * digests in pinned memory that the kernels read and write in place, and calls of <= 1024 digests
+ * poll it instead of waiting for the stream (NWC_SPIN_WAIT=0 turns that off). */
+/* generate_keypair: seed = 32 bytes of the CALLER's CSPRNG -> secret64 = seed || A
+ * (Keypair::to_bytes).  seed and secret64 may overlap at secret64[0]. */
+int nwc_keypair_from_seed(const uint8_t seed[32], uint8_t secret64[64]);
+/* SignatureService::new / Keypair::from_bytes.  NULL on failure (nwc_last_error,
+ * nwc_last_error_code). */
+void* nwc_signer_create(const uint8_t secret64[64]);
+int nwc_signer_public_key(const void* signer, uint8_t pk[32]);
+/* Signature::new(digest, secret) */
+int nwc_signer_sign(void* signer, const uint8_t msg32[32], uint8_t sig[64]);
+/* n digests msgs32[32 i] -> sigs[64 i] in one launch (a round's votes; what a SignatureService
+ * drains from its queue) */
+int nwc_signer_sign_many(void* signer, const uint8_t* msgs32, size_t n, uint8_t* sigs);
+/* Device-resident: d_msgs (16-byte aligned) holds digest i at msg_stride * i, msg_stride = 32, or
+ * 0 for one digest signed n times; d_sigs n x 64 B.  Asynchronous on `stream`.  n < 2^31. */
+int nwc_dev_sign(void* signer, const void* d_msgs, uint64_t msg_stride, uint64_t n, void* d_sigs, void* stream);
+/* Overwrites the key record with zeros (a memset on the signer's device stream, waited for), then
+ * frees it; waits for the device first, so launches of nwc_dev_sign still in flight finish.  No
+ * call on the signer may start after destroy.  nwc_shutdown does the same to signers still alive,
+ * which then answer NWC_ERR_NOT_INIT; destroy them afterwards all the same. */
+int nwc_signer_destroy(void* signer);
 
 /* Committee key cache (config/src/lib.rs:154-156 Committee).  Optional: verdicts never
  * depend on it. */
@@ -318,7 +372,8 @@ int nwc_dev_sha512_trunc32(const void* d_data, const void* d_offsets, uint64_t n
 int nwc_dev_sha512_trunc32_ranges(const void* d_data, const void* d_starts, const void* d_ends, uint64_t n,
                                   void* d_out32, void* stream);
 /* Synthetic workload generation (BASELINE configs 2/3/5): out_i = SHA-512(tag||u64le(first+i))[..32]
- * and RFC 8032 keygen+sign of (seed_i, msg_i). */
+ * and RFC 8032 keygen+sign of (seed_i, msg_i): a key per lane, derived anew on every call.  For
+ * signing with a node's key use a signer (above). */
 int nwc_dev_derive32(const uint8_t* tag, int taglen, uint64_t first, uint64_t n, void* d_out,
                      void* stream);
 int nwc_dev_keygen_sign(const void* d_seeds, const void* d_msgs, uint64_t n, void* d_pks,

@@ -28,6 +28,7 @@ _SIGS = {
     "nwc_init": (ctypes.c_int, [ctypes.c_uint32]),
     "nwc_shutdown": (None, []),
     "nwc_last_error": (ctypes.c_char_p, []),
+    "nwc_last_error_code": (ctypes.c_int, []),
     "nwc_version": (ctypes.c_int, []),
     "nwc_device_count": (ctypes.c_int, []),
     "nwc_build_id": (ctypes.c_char_p, []),
@@ -47,6 +48,14 @@ _SIGS = {
                                                 ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                 ctypes.c_void_p]),
     "nwc_msm_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "nwc_keypair_from_seed": (ctypes.c_int, [_c_u8p, _c_u8p]),
+    "nwc_signer_create": (ctypes.c_void_p, [_c_u8p]),
+    "nwc_signer_public_key": (ctypes.c_int, [ctypes.c_void_p, _c_u8p]),
+    "nwc_signer_sign": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, _c_u8p]),
+    "nwc_signer_sign_many": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, ctypes.c_size_t, _c_u8p]),
+    "nwc_dev_sign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                    ctypes.c_void_p, ctypes.c_void_p]),
+    "nwc_signer_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "nwc_set_committee": (ctypes.c_int, [_c_u8p, ctypes.c_size_t]),
     "nwc_cache_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "nwc_auto_cache_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
@@ -114,7 +123,7 @@ def memory_info() -> dict:
 
 
 def diag_set(name: str, value: int) -> None:
-    """nwc_diag_set: a test / A-B knob ("straus_nq", "force_windows")."""
+    """nwc_diag_set: a test / A-B knob ("straus_nq", "force_windows", "sign_path", ...)."""
     check(load().nwc_diag_set(name.encode(), value))
 
 

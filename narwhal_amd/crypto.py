@@ -9,6 +9,7 @@ like crypto/src/tests/crypto_tests.rs:
   SecretKey         lib.rs:120-161   64 bytes (seed || public), zeroised on drop
   generate_keypair  lib.rs:167-175
   Signature         lib.rs:177-219   new / verify / verify_batch, Default = 64 zero bytes
+  SignatureService  lib.rs:222-250   request_signature; a Signer is the registered key behind it
   CryptoError       lib.rs:18        opaque verification failure (Rust `Err`)
 Device/runtime failures raise `DeviceError` -- never `CryptoError`.
 Verification, hashing and signing all run on the GPU; there is no CPU path here.
@@ -18,13 +19,15 @@ from __future__ import annotations
 import base64
 import ctypes
 import os
+import threading
 from typing import Iterable, Optional, Sequence, Tuple
 
 from . import _lib
 from ._lib import DeviceError
 
 __all__ = ["CryptoError", "DeviceError", "Digest", "Hash", "PublicKey", "SecretKey", "Signature",
-           "generate_keypair", "generate_production_keypair", "digest_bytes", "digest_many"]
+           "generate_keypair", "generate_production_keypair", "digest_bytes", "digest_many", "Signer",
+           "SignatureService", "keypair_from_seed"]
 
 
 class CryptoError(Exception):
@@ -249,3 +252,151 @@ class Signature:
 
     def __repr__(self) -> str:
         return "Signature { part1: %s, part2: %s }" % (list(self.part1), list(self.part2))
+
+
+def _secret_bytes(secret) -> bytes:
+    return bytes(secret._b) if isinstance(secret, SecretKey) else bytes(secret)
+
+
+def keypair_from_seed(seed: bytes) -> Tuple[PublicKey, SecretKey]:
+    """nwc_keypair_from_seed: (A, seed || A) for 32 seed bytes of the caller's CSPRNG."""
+    if len(seed) != 32:
+        raise ValueError("seed must be 32 bytes")
+    lib = _lib.load()
+    out = ctypes.create_string_buffer(64)
+    _lib.check(lib.nwc_keypair_from_seed(_lib.buf(bytes(seed)), out))
+    return PublicKey(out.raw[32:]), SecretKey(out.raw)
+
+
+class Signer:
+    """A registered signing key (nwc_signer): the key is expanded once into device memory and every
+    signature after that is one launch of a sign kernel.  A context manager; `close()` (or leaving
+    the `with` block) zeroes and frees the device copy.  Raises DeviceError for a secret whose
+    public half is not the seed's (a deliberate deviation from dalek's Keypair::from_bytes)."""
+
+    def __init__(self, secret):
+        b = _secret_bytes(secret)
+        if len(b) != 64:
+            raise ValueError("SecretKey must be 64 bytes")
+        self._lib = _lib.load()
+        self.handle = self._lib.nwc_signer_create(_lib.buf(b))
+        if not self.handle:
+            raise DeviceError("nwc_signer_create failed (%d): %s" % (self._lib.nwc_last_error_code(),
+                                                                     self._lib.nwc_last_error().decode()))
+
+    def public_key(self) -> PublicKey:
+        out = ctypes.create_string_buffer(32)
+        _lib.check(self._lib.nwc_signer_public_key(self.handle, out))
+        return PublicKey(out.raw)
+
+    def sign(self, digest) -> "Signature":
+        """`Signature::new(digest, secret)` with the registered key."""
+        d = digest.to_vec() if isinstance(digest, Digest) else bytes(digest)
+        if len(d) != 32:
+            raise ValueError("Digest must be 32 bytes")
+        out = ctypes.create_string_buffer(64)
+        _lib.check(self._lib.nwc_signer_sign(self.handle, _lib.buf(d), out))
+        return Signature.from_bytes(out.raw)
+
+    def sign_many(self, digests: Sequence) -> list:
+        """One launch for all of `digests` (a round's votes)."""
+        ds = [d.to_vec() if isinstance(d, Digest) else bytes(d) for d in digests]
+        if any(len(d) != 32 for d in ds):
+            raise ValueError("Digest must be 32 bytes")
+        n = len(ds)
+        if n == 0:
+            return []
+        out = ctypes.create_string_buffer(64 * n)
+        _lib.check(self._lib.nwc_signer_sign_many(self.handle, _lib.buf(b"".join(ds)), n, out))
+        raw = out.raw
+        return [Signature.from_bytes(raw[64 * i:64 * i + 64]) for i in range(n)]
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.nwc_signer_destroy(h))
+
+    def __enter__(self) -> "Signer":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter teardown)
+            pass
+
+
+class SignatureService:
+    """`SignatureService` (lib.rs:222-250): `request_signature(digest)` blocks until the signature
+    is there.  One worker thread drains every request queued so far into one `sign_many` launch;
+    requests that arrive while a launch is in flight go out together in the next one.  `signer`
+    (anything with `sign_many(list of digests) -> list of Signatures`) replaces the GPU signer, so
+    the queue can be exercised without a device; a signer the service created is closed by
+    `close()`."""
+
+    def __init__(self, secret=None, signer=None):
+        self._own = signer is None
+        self._signer = Signer(secret) if signer is None else signer
+        self._cv = threading.Condition()
+        self._queue = []          # [digest, result slot]
+        self._closed = False
+        self._requests = 0
+        self._launches = 0
+        self._thread = threading.Thread(target=self._run, name="nwc-signature-service", daemon=True)
+        self._thread.start()
+
+    def _run(self) -> None:
+        while True:
+            with self._cv:
+                while not self._queue and not self._closed:
+                    self._cv.wait()
+                if not self._queue:
+                    return
+                batch, self._queue = self._queue, []
+                self._launches += 1
+            try:
+                sigs = self._signer.sign_many([d for d, _ in batch])
+                if len(sigs) != len(batch):
+                    raise DeviceError("sign_many returned %d signatures for %d digests" % (len(sigs), len(batch)))
+                for (_, slot), sig in zip(batch, sigs):
+                    slot["sig"] = sig
+            except Exception as e:  # noqa: BLE001  (handed to every waiting caller)
+                for _, slot in batch:
+                    slot["err"] = e
+            for _, slot in batch:
+                slot["done"].set()
+
+    def request_signature(self, digest) -> "Signature":
+        slot = {"done": threading.Event()}
+        with self._cv:
+            if self._closed:
+                raise DeviceError("SignatureService is closed")
+            self._queue.append((digest, slot))
+            self._requests += 1
+            self._cv.notify()
+        slot["done"].wait()
+        if "err" in slot:
+            raise slot["err"]
+        return slot["sig"]
+
+    def stats(self) -> dict:
+        with self._cv:
+            return {"requests": self._requests, "launches": self._launches}
+
+    def close(self) -> None:
+        """Signs what is queued, stops the worker and closes a signer the service created."""
+        with self._cv:
+            self._closed = True
+            self._cv.notify()
+        self._thread.join()
+        if self._own:
+            self._signer.close()
+
+    def __enter__(self) -> "SignatureService":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()

@@ -9,6 +9,7 @@
 //   k_cert_index         vote -> certificate index of a host call's votes, from the offsets
 //   k_sha512_digest32    Sha512::digest(batch)[..32] per message (worker/src/processor.rs:38)
 //   k_keygen_sign        synthetic (pk, sig) generation (RFC 8032 == dalek sign) for workloads
+//   k_sign / k_sign_wide signing with a registered key (sign.h)
 //
 // Verification per lane:
 //   1. s < l                                       (A.1)
@@ -2455,6 +2456,7 @@ __global__ __launch_bounds__(256) void k_keygen_sign(const uint8_t* __restrict__
 #include "straus.h"
 #include "msm.h"
 #include "resolve.h"
+#include "sign.h"
 namespace nwc {
 
 // Seeds / messages of the synthetic workloads (SURVEY.md §8(d) cfg 2):

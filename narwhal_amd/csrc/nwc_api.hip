@@ -36,6 +36,7 @@ namespace {
 
 thread_local std::string t_err;
 thread_local int t_dev = 0;
+thread_local int t_code = 0;   // code of the calling thread's last error (nwc_last_error_code)
 
 int set_err(int code, const char* fmt, ...) {
   char buf[512];
@@ -44,6 +45,7 @@ int set_err(int code, const char* fmt, ...) {
   vsnprintf(buf, sizeof buf, fmt, ap);
   va_end(ap);
   t_err = buf;
+  t_code = code;
   return code;
 }
 
@@ -119,6 +121,7 @@ struct DevCtx {
   std::vector<hipEvent_t> ev_chunk;
   std::vector<hipEvent_t> ev_cnt;      // sanitize: chunk k's vote count copied to the host
   nwc::ge_niels* base_table = nullptr;
+  nwc::ge_niels* sign_table = nullptr;   // the signers' basepoint table (60 KB, sign.h), built by the first signer
   nwc::ge_niels_pad* base24 = nullptr;   // radix-2^24 basepoint tables (2.1 GB)
   nwc::ge_p3* base24_points = nullptr;    // B and 2^141 B
   nwc::ge_niels_pad* comb_base = nullptr;   // radix-256 basepoint comb (528 KB): latency kernel
@@ -286,6 +289,7 @@ struct Carve {
 };
 
 uint32_t auto_keys_cap();
+void signers_shutdown();
 int auto_grow(DevCtx& d, uint32_t ncap);
 bool comb16_enabled();
 
@@ -298,6 +302,7 @@ struct Knobs {
   std::atomic<uint32_t> launch_keys{1};   // NWC_LAUNCH_KEYS: 0 = large batch-leaf launches never build launch keys
   std::atomic<uint32_t> msm_group{0};     // NWC_MSM_GROUP: votes per Pippenger group of k_verify_msm (0 = sized per launch)
   std::atomic<uint32_t> msm_adapt{1};     // NWC_MSM_ADAPT: 0 = the equation on every group (no skip policy)
+  std::atomic<uint32_t> sign_path{0};     // tests: 0 = by size (NWC_SIGN_WIDE_MAX), 1 = k_sign, 2 = k_sign_wide
   std::atomic<uint64_t> dalek_seed{0};    // tests: fixed seed of the per-certificate equation's z_i (0 = host CSPRNG)
   Knobs() {
     if (const char* e = std::getenv("NWC_LAUNCH_KEYS")) launch_keys = (uint32_t)std::strtoul(e, nullptr, 10);
@@ -1954,7 +1959,7 @@ int nwc_cert_cuts(const uint32_t* offsets, size_t m, uint32_t world, uint64_t* c
   return 0;
 }
 
-int nwc_version(void) { return (1 << 16) | 1; }
+int nwc_version(void) { return (1 << 16) | 2; }
 
 #ifndef NWC_BUILD_ID
 #define NWC_BUILD_ID "unknown"
@@ -1979,6 +1984,9 @@ int nwc_diag_set(const char* name, int64_t value) {
     knobs().msm_adapt = (uint32_t)value;
   } else if (std::strcmp(name, "dalek_seed") == 0) {
     knobs().dalek_seed = (uint64_t)value;
+  } else if (std::strcmp(name, "sign_path") == 0) {
+    if (value > 2) return set_err(NWC_ERR_ARG, "sign_path must be 0 (by size), 1 (k_sign) or 2 (k_sign_wide)");
+    knobs().sign_path = (uint32_t)value;
   } else if (std::strcmp(name, "launch_keys") == 0) {
     if (value > 1) return set_err(NWC_ERR_ARG, "launch_keys must be 0 or 1");
     knobs().launch_keys = (uint32_t)value;
@@ -2034,10 +2042,12 @@ int nwc_init(uint32_t device_mask) {
 
 void nwc_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_mu);
+  signers_shutdown();   // live signers' key records are zeroed and freed first
   for (auto& d : g_devs) {
     std::lock_guard<std::mutex> dl(d->mu);
     (void)hipSetDevice(d->hip_id);
     if (d->stream) (void)hipStreamSynchronize(d->stream);
+    if (d->sign_table) (void)hipFree(d->sign_table);
     if (d->arena) (void)hipFree(d->arena);
     if (d->scratch) (void)hipFree(d->scratch);
     if (d->fb_list) (void)hipFree(d->fb_list);
@@ -3104,6 +3114,7 @@ int nwc_dev_sanitize_messages(const void* d_data, const void* d_offsets, uint64_
 }  // extern "C"
 
 #include "digester.h"
+#include "signer.h"
 
 extern "C" {
 
@@ -3122,6 +3133,7 @@ int nwc_memory_info(nwc_memory* out) {
                   2 * sizeof(nwc::ge_p3) + nwc::BaseComb::per * sizeof(nwc::ge_niels_pad) +
                   (d.comb16 ? nwc::COMB16_TOTAL * sizeof(nwc::ge_niels_pad) + nwc::COMB16_WINDOWS * sizeof(nwc::ge_p3) : 0) +
                   36 * (size_t)NWC_MEMO_SLOTS;
+    if (d.sign_table) out->tables += nwc::SIGN_TABLE_BYTES;   // a process that only signs holds this one alone
     out->committee = d.cm_bytes;
     out->auto_cache = (size_t)d.ak_cap * (36 + 129 * sizeof(nwc::ge_niels) + nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad)) +
                       4 * (size_t)d.ak_slot_cap + d.kb_cap * sizeof(nwc::ge_p3) +

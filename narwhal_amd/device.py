@@ -161,6 +161,27 @@ def keygen_sign_host(seeds: bytes, msgs: bytes, n: int) -> Tuple[bytes, bytes]:
     return bytes(pks.cpu().numpy().tobytes()), bytes(sigs.cpu().numpy().tobytes())
 
 
+def sign(signer, msgs: torch.Tensor, out: Optional[torch.Tensor] = None, n: Optional[int] = None) -> torch.Tensor:
+    """nwc_dev_sign: signatures [n, 64] of the HBM-resident digests msgs[n, 32] under `signer` (a
+    crypto.Signer or a raw handle).  A single digest (32 bytes) with n given is signed n times
+    (msg_stride 0).  Asynchronous on the current stream."""
+    lib = _lib.load()
+    handle = getattr(signer, "handle", signer)
+    assert msgs.dtype == torch.uint8 and msgs.numel() % 32 == 0
+    stride = 32
+    if n is None:
+        n = msgs.numel() // 32
+    elif msgs.numel() == 32:
+        stride = 0
+    else:
+        assert msgs.numel() >= 32 * n
+    if out is None:
+        out = torch.empty((n, 64), dtype=torch.uint8, device=msgs.device)
+    assert out.dtype == torch.uint8 and out.numel() >= 64 * n
+    _lib.check(lib.nwc_dev_sign(handle, _ptr(msgs) if n else None, stride, n, _ptr(out) if n else None, _stream()))
+    return out
+
+
 def unpack_bits(words: torch.Tensor, n: int):
     """Verdict words -> numpy bool array of length n (host)."""
     import numpy as np

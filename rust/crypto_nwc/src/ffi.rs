@@ -26,6 +26,7 @@ extern "C" {
     pub fn nwc_init(device_mask: u32) -> c_int;
     pub fn nwc_shutdown();
     pub fn nwc_last_error() -> *const c_char;
+    pub fn nwc_last_error_code() -> c_int;
     pub fn nwc_version() -> c_int;
     pub fn nwc_device_count() -> c_int;
     pub fn nwc_build_id() -> *const c_char;
@@ -46,6 +47,14 @@ extern "C" {
                                         m: usize, cert_ok_bitmap: *mut u8, bad_vote_bitmap: *mut u8) -> c_int;
     pub fn nwc_verify_batch_msm_many(digests: *const u8, offsets: *const u32, pks: *const u8, sigs: *const u8,
                                         m: usize, cert_ok_bitmap: *mut u8, bad_vote_bitmap: *mut u8) -> c_int;
+    pub fn nwc_keypair_from_seed(seed: *const u8, secret64: *mut u8) -> c_int;
+    pub fn nwc_signer_create(secret64: *const u8) -> *mut c_void;
+    pub fn nwc_signer_public_key(signer: *const c_void, pk: *mut u8) -> c_int;
+    pub fn nwc_signer_sign(signer: *mut c_void, msg32: *const u8, sig: *mut u8) -> c_int;
+    pub fn nwc_signer_sign_many(signer: *mut c_void, msgs32: *const u8, n: usize, sigs: *mut u8) -> c_int;
+    pub fn nwc_dev_sign(signer: *mut c_void, d_msgs: *const c_void, msg_stride: u64, n: u64, d_sigs: *mut c_void,
+                        stream: *mut c_void) -> c_int;
+    pub fn nwc_signer_destroy(signer: *mut c_void) -> c_int;
     pub fn nwc_set_committee(pks: *const u8, n: usize) -> c_int;
     pub fn nwc_cache_stats(committee_keys: *mut u32, auto_keys: *mut u32) -> c_int;
     pub fn nwc_auto_cache_info(capacity: *mut u32, builds: *mut u64, hits: *mut u64) -> c_int;

@@ -18,6 +18,8 @@
 //! }
 //! // worker/src/processor.rs:38
 //! let digest = Digest(crypto_nwc::digest32(&batch));
+//! // crypto/src/lib.rs:180-191  Signature::new, with a Signer made once from the node's SecretKey
+//! let sig = signer.sign(&digest.0);   // part1 = sig[..32], part2 = sig[32..]
 //! ```
 //!
 //! Return convention of the C ABI: 0 = valid, 1 = invalid, < 0 = device/runtime failure, which
@@ -172,5 +174,70 @@ impl BatchDigester {
 impl Drop for BatchDigester {
     fn drop(&mut self) {
         unsafe { ffi::nwc_digester_destroy(self.q) };
+    }
+}
+
+/// `generate_keypair` (crypto/src/lib.rs:167-175): `seed || A` (dalek `Keypair::to_bytes`) for 32
+/// bytes of the caller's CSPRNG.
+pub fn keypair_from_seed(seed: &[u8; 32]) -> [u8; 64] {
+    init(0);
+    let mut out = [0u8; 64];
+    check(unsafe { ffi::nwc_keypair_from_seed(seed.as_ptr(), out.as_mut_ptr()) });
+    out
+}
+
+/// A registered signing key (`nwc_signer`): what `Signature::new` and `SignatureService`
+/// (crypto/src/lib.rs:180-191, 222-250) sign with.  The key is expanded once into device memory;
+/// dropping the signer zeroes and frees that copy.  Unlike dalek 1.0.1's `Keypair::from_bytes`,
+/// `new` refuses a secret whose public half is not the seed's (`None`).
+pub struct Signer {
+    h: *mut std::os::raw::c_void,
+}
+
+unsafe impl Send for Signer {}
+unsafe impl Sync for Signer {}   // libnwc serialises calls on one signer
+
+impl Signer {
+    /// `secret64` = `SecretKey` bytes (seed || public key).  `None` for a mismatched public half;
+    /// panics on a device failure.
+    pub fn new(secret64: &[u8; 64]) -> Option<Self> {
+        init(0);
+        let h = unsafe { ffi::nwc_signer_create(secret64.as_ptr()) };
+        if h.is_null() {
+            if unsafe { ffi::nwc_last_error_code() } == -2 {
+                return None;
+            }
+            let msg = unsafe { CStr::from_ptr(ffi::nwc_last_error()) };
+            panic!("libnwc signer: {}", msg.to_string_lossy());
+        }
+        Some(Signer { h })
+    }
+
+    pub fn public_key(&self) -> [u8; 32] {
+        let mut pk = [0u8; 32];
+        check(unsafe { ffi::nwc_signer_public_key(self.h, pk.as_mut_ptr()) });
+        pk
+    }
+
+    /// `Signature::new(digest, secret)`: R || s.
+    pub fn sign(&self, digest: &[u8; 32]) -> [u8; 64] {
+        let mut sig = [0u8; 64];
+        check(unsafe { ffi::nwc_signer_sign(self.h, digest.as_ptr(), sig.as_mut_ptr()) });
+        sig
+    }
+
+    /// One launch for all of `digests`: what a `SignatureService` task drains from its channel.
+    pub fn sign_many(&self, digests: &[[u8; 32]]) -> Vec<[u8; 64]> {
+        let mut sigs = vec![[0u8; 64]; digests.len()];
+        check(unsafe {
+            ffi::nwc_signer_sign_many(self.h, digests.as_ptr() as *const u8, digests.len(), sigs.as_mut_ptr() as *mut u8)
+        });
+        sigs
+    }
+}
+
+impl Drop for Signer {
+    fn drop(&mut self) {
+        unsafe { ffi::nwc_signer_destroy(self.h) };
     }
 }
