@@ -195,6 +195,56 @@ int nwc_dev_sign(void* signer, const void* d_msgs, uint64_t msg_stride, uint64_t
  * which then answer NWC_ERR_NOT_INIT; destroy them afterwards all the same. */
 int nwc_signer_destroy(void* signer);
 
+/* ---- concurrent small verify calls behind one launch -------------------------------------- */
+/* Every verification a primary makes is a small call: Signature::verify is one equation
+ * (crypto/src/lib.rs:200-204; Header::verify and Vote::verify, primary/src/messages.rs:63-66,
+ * 138-141), Signature::verify_batch one certificate (crypto/src/lib.rs:206-219;
+ * Certificate::verify, primary/src/messages.rs:214) -- and the reference makes them from many tokio
+ * tasks at once (node/src/main.rs:17, worker/src/worker.rs:182,227).  nwc_verify_strict and
+ * nwc_verify_batch answer such calls one at a time per device.  A verifier is an opaque handle
+ * (void*, as a signer) bound to the calling thread's device (nwc_dev_set_device), like a
+ * digester: concurrent blocking calls on one verifier are packed into GROUPS that share a launch,
+ * and each caller returns as soon as its own verdict bytes are in.  Opt-in; the plain entries are
+ * unchanged.
+ *
+ * Verdicts and bad sets are exactly those of nwc_verify_strict / nwc_verify_batch on the same
+ * inputs (dalek verify_strict; the exact batch leaves, Err on the randomized domain): every
+ * equation carries its own mode into the shared launch.
+ *
+ * A group closes when it holds max_requests requests (0 = as many as fit), when the next request's
+ * equations do not fit its capacity (4,096 equations; NWC_VERIFIER_GROUP_EQ in the environment, read
+ * by the first create), or when max_wait_us have passed since its first request arrived.
+ * max_wait_us == 0 never waits for company: a group is then whatever arrived while the previous
+ * group was in flight, and a lone caller launches at once.  Two group buffers of coherent pinned
+ * host memory (145 B per equation of capacity: 0.6 MB each by default) are read in place by the
+ * kernels; a verifier holds no device memory of its own.
+ *
+ * Conventions as everywhere here: both verify calls block and may be made from any number of
+ * threads; n == 0 is Ok at once; null pointers give NWC_ERR_ARG; NWC_ERR_NOT_INIT before nwc_init; a
+ * request of more than 1,024 votes (or more than a group holds) is handed to nwc_verify_batch
+ * (bypassed_requests).  A device error in a group reaches exactly that group's callers as a code
+ * < 0, never as "invalid".  destroy lets queued requests finish, wakes blocked callers and waits
+ * for them to leave (no call on the verifier may start after destroy); nwc_shutdown does the same
+ * to verifiers still alive, which then answer NWC_ERR_NOT_INIT; destroy them afterwards all the
+ * same.  create returns NULL on failure (nwc_last_error, nwc_last_error_code). */
+typedef struct nwc_verifier_stats_t {
+  uint64_t groups, requests, equations, wide_equations, cold_equations, redone_equations, bypassed_requests,
+      max_requests_in_group;
+} nwc_verifier_stats_t;
+void* nwc_verifier_create(uint32_t max_requests, uint32_t max_wait_us);
+/* Signature::verify: 0 valid, 1 invalid, < 0 error */
+int nwc_verifier_verify_strict(void* verifier, const uint8_t msg32[32], const uint8_t pk[32], const uint8_t sig[64]);
+/* Signature::verify_batch(digest, votes): as nwc_verify_batch, bad_bitmap nullable */
+int nwc_verifier_verify_batch(void* verifier, const uint8_t msg32[32], const uint8_t* pks, const uint8_t* sigs, size_t n,
+                              uint8_t* bad_bitmap);
+/* out: eight uint64_t laid out as nwc_verifier_stats_t.  requests / equations are counted when a
+ * request joins a group, the rest when the group launches: groups = launches shared; wide /
+ * cold_equations = equations whose key a cache held / first-sight equations; redone_equations =
+ * equations decided again on the general path (a key missing on the device after all, a failed
+ * lattice reduction, an unwritten verdict byte). */
+int nwc_verifier_stats(void* verifier, uint64_t* out);
+int nwc_verifier_destroy(void* verifier);
+
 /* Committee key cache (config/src/lib.rs:154-156 Committee).  Optional: verdicts never
  * depend on it. */
 int nwc_set_committee(const uint8_t* pks, size_t n);

@@ -27,7 +27,7 @@ from ._lib import DeviceError
 
 __all__ = ["CryptoError", "DeviceError", "Digest", "Hash", "PublicKey", "SecretKey", "Signature",
            "generate_keypair", "generate_production_keypair", "digest_bytes", "digest_many", "Signer",
-           "SignatureService", "keypair_from_seed"]
+           "SignatureService", "keypair_from_seed", "Verifier"]
 
 
 class CryptoError(Exception):
@@ -400,3 +400,73 @@ class SignatureService:
 
     def __exit__(self, *exc) -> None:
         self.close()
+
+
+class Verifier:
+    """Concurrent small verify calls behind shared launches (nwc_verifier): `verify` and
+    `verify_batch` block like `Signature.verify` / `Signature.verify_batch` and raise CryptoError as
+    they do, but calls made from several threads at once are packed into groups that share one
+    launch.  A group closes at `max_requests` requests (0 = as many as fit), when it is full, or
+    `max_wait_us` after its first request (0 = never wait for company).  A context manager;
+    `close()` lets queued requests finish.  `lib`: a loaded library (tests)."""
+
+    STATS = ("groups", "requests", "equations", "wide_equations", "cold_equations", "redone_equations",
+             "bypassed_requests", "max_requests_in_group")
+
+    def __init__(self, max_requests: int = 0, max_wait_us: int = 0, lib=None):
+        self._lib = lib if lib is not None else _lib.load()
+        self.handle = self._lib.nwc_verifier_create(max_requests, max_wait_us)
+        if not self.handle:
+            raise DeviceError("nwc_verifier_create failed (%d): %s" % (self._lib.nwc_last_error_code(),
+                                                                       self._lib.nwc_last_error().decode()))
+
+    def verify(self, digest, public_key, signature) -> None:
+        """`Signature::verify` -> dalek verify_strict.  Raises CryptoError on an invalid signature."""
+        d = digest.to_vec() if isinstance(digest, Digest) else bytes(digest)
+        if len(d) != 32:
+            raise ValueError("Digest must be 32 bytes")
+        rc = _lib.check(self._lib.nwc_verifier_verify_strict(self.handle, _lib.buf(d), _lib.buf(bytes(public_key)),
+                                                             _lib.buf(signature.flatten())))
+        if rc != _lib.NWC_OK:
+            raise CryptoError("signature verification failed")
+
+    def verify_batch(self, digest, votes: Iterable[Tuple[PublicKey, "Signature"]], bad: Optional[list] = None) -> None:
+        """`Signature::verify_batch(digest, votes)`.  Raises CryptoError if any vote fails; a list
+        `bad` receives the indices of the failing votes."""
+        d = digest.to_vec() if isinstance(digest, Digest) else bytes(digest)
+        if len(d) != 32:
+            raise ValueError("Digest must be 32 bytes")
+        votes = list(votes)
+        n = len(votes)
+        pks = b"".join(bytes(p) for p, _ in votes)
+        sigs = b"".join(s.flatten() for _, s in votes)
+        bitmap = ctypes.create_string_buffer((n + 7) // 8 or 1)
+        rc = _lib.check(self._lib.nwc_verifier_verify_batch(self.handle, _lib.buf(d), _lib.buf(pks) if n else None,
+                                                            _lib.buf(sigs) if n else None, n, bitmap))
+        if bad is not None:
+            raw = bitmap.raw
+            bad.extend(i for i in range(n) if (raw[i >> 3] >> (i & 7)) & 1)
+        if rc != _lib.NWC_OK:
+            raise CryptoError("batch verification failed")
+
+    def stats(self) -> dict:
+        out = (ctypes.c_uint64 * len(self.STATS))()
+        _lib.check(self._lib.nwc_verifier_stats(self.handle, out))
+        return {k: int(v) for k, v in zip(self.STATS, out)}
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.nwc_verifier_destroy(h))
+
+    def __enter__(self) -> "Verifier":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter teardown)
+            pass

@@ -1864,13 +1864,16 @@ __device__ __forceinline__ void cold_store_p2(i32 (*q)[10], const gs_p2& p) {
 // vbytes != nullptr: zero-copy launch (inputs in pinned host memory), one verdict byte per
 // equation stored straight to the host like k_verify_comb_wide's (bit 7 written, bit 0 valid, bit
 // 1 = the reduction failed: the host re-runs the staged path, whose fallback kernel decides it)
-__global__ __launch_bounds__(256) void k_verify_cold(VerifyArgs a, const ge_niels_pad* __restrict__ comb16,
-                                                    uint8_t* vbytes) {
+//
+// The body is shared with k_verify_group_cold (below): i = the equation this block decides, mode =
+// its mode (0 = batch leaf, else strict).  Both are block-uniform; `leaf` gates work inside the
+// waves' branches only, so the number of __syncthreads a wave meets (two) does not depend on the
+// mode.
+__device__ __forceinline__ void verify_cold_body(const VerifyArgs& a, const ge_niels_pad* __restrict__ comb16,
+                                                 uint8_t* vbytes, const uint64_t i, const int mode) {
   __shared__ ColdShared sh;
-  const uint64_t i = blockIdx.x;
-  if (i >= a.n) return;   // block-uniform
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const bool leaf = a.strict == 0;
+  const bool leaf = mode == 0;
   if (threadIdx.x == 0) sh.ready = 0;
   __syncthreads();
 #define CT(tag) do {} while (0)
@@ -2013,7 +2016,7 @@ __global__ __launch_bounds__(256) void k_verify_cold(VerifyArgs a, const ge_niel
     torsion = sh.a_ok && !same;
   }
   if (lane == 0) {
-    const bool strict = a.strict != 0;
+    const bool strict = mode != 0;
     const bool ok = sh.s_ok && sh.a_ok && sh.r_ok && !(strict && (sh.a_small || sh.r_small));
     const bool fb = !torsion && (!sh.lat_ok || (a.force_fb_every && (i % a.force_fb_every) == 0));
     if (vbytes) {
@@ -2029,11 +2032,46 @@ __global__ __launch_bounds__(256) void k_verify_cold(VerifyArgs a, const ge_niel
   }
 }
 
-__global__ __launch_bounds__(128) void k_verify_comb_wide(VerifyArgs a, CombArgs ca) {
-  __shared__ fe sh_rx, sh_ry;
-  __shared__ int sh_rok;
+__global__ __launch_bounds__(256) void k_verify_cold(VerifyArgs a, const ge_niels_pad* __restrict__ comb16,
+                                                    uint8_t* vbytes) {
   const uint64_t i = blockIdx.x;
   if (i >= a.n) return;   // block-uniform
+  verify_cold_body(a, comb16, vbytes, i, a.strict);
+}
+
+// ---- groups of small host calls (verifier.h): one launch decides equations of many requests ----
+// A group's equations lie in one pinned host buffer (a.msgs / msg_index / pks / sigs, a.n of them);
+// block b decides equation list[b], b < count, under that equation's own mode byte (bit 0 = strict
+// verification, clear = batch leaf) and stores its verdict byte to vbytes[list[b]] (bit 7 written,
+// bit 0 valid, bit 1 = decide me again).  The mode is read through a scalar register, so every wave
+// of the block branches on the same value.
+struct GroupArgs {
+  const uint32_t* list;
+  const uint8_t* modes;
+  uint8_t* vbytes;
+  uint32_t count;
+};
+__device__ __forceinline__ bool group_equation(const VerifyArgs& a, const GroupArgs& g, uint64_t& i, int& mode) {
+  if (blockIdx.x >= g.count) return false;   // block-uniform
+  const uint32_t e = g.list[blockIdx.x];
+  if (e >= a.n) return false;                // block-uniform; never indexes past the group's buffers
+  i = e;
+  mode = __builtin_amdgcn_readfirstlane((int)(g.modes[e] & 1u));
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_verify_group_cold(VerifyArgs a, const ge_niels_pad* __restrict__ comb16,
+                                                          GroupArgs g) {
+  uint64_t i;
+  int mode;
+  if (!group_equation(a, g, i, mode)) return;
+  verify_cold_body(a, comb16, g.vbytes, i, mode);
+}
+
+// k_verify_comb_wide's body, shared with k_verify_group_wide: i = the equation this block decides,
+// mode = 0 batch leaf, else strict (block-uniform both); vbytes as CombArgs::vbytes.
+__device__ __forceinline__ void verify_wide_body(const VerifyArgs& a, const CombArgs& ca, uint8_t* vbytes, const uint64_t i,
+                                                 const int mode, fe& sh_rx, fe& sh_ry, int& sh_rok) {
   const Committee& cm = a.committee;
   u32 mw[8], aw[8], sgw[16];
   load_inputs(a, i, mw, aw, sgw);
@@ -2053,7 +2091,7 @@ __global__ __launch_bounds__(128) void k_verify_comb_wide(VerifyArgs a, CombArgs
     if (lane == 0) {
       sh_rx = X;
       sh_ry = Y;
-      sh_rok = ok && !(a.strict && ycanon_is_small_order(yc));
+      sh_rok = ok && !(mode && ycanon_is_small_order(yc));
     }
   } else {
     // lanes 0..31: basepoint comb (radix 2^8) windows; lanes 32..32+W-1: key comb windows (W = 19)
@@ -2080,13 +2118,13 @@ __global__ __launch_bounds__(128) void k_verify_comb_wide(VerifyArgs a, CombArgs
   __syncthreads();
   if (threadIdx.x == 0) {
     const u32 fl = cm.flags[kk];
-    const bool flags_ok = key >= 0 && sc_lt_l(sw) && key_flags_ok(fl, a.strict != 0) && sh_rok;
+    const bool flags_ok = key >= 0 && sc_lt_l(sw) && key_flags_ok(fl, mode != 0) && sh_rok;
     const bool eq = fe_is_zero(fe_sub(sum.X, fe_mul(sh_rx, sum.Z))) && fe_is_zero(fe_sub(sum.Y, fe_mul(sh_ry, sum.Z)));
-    if (ca.vbytes) {
+    if (vbytes) {
       // zero-copy latency launch: one byte per equation straight into pinned host memory; bit 7
       // marks it written, and the system-scope store goes out at once, so the host can return as
       // soon as every byte is in (no wait for the stream's completion signal)
-      __hip_atomic_store(ca.vbytes + i, (uint8_t)(0x80u | (flags_ok && eq ? 1u : 0u) | (key < 0 ? 2u : 0u)),
+      __hip_atomic_store(vbytes + i, (uint8_t)(0x80u | (flags_ok && eq ? 1u : 0u) | (key < 0 ? 2u : 0u)),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     } else {
       if (key < 0) {
@@ -2096,6 +2134,25 @@ __global__ __launch_bounds__(128) void k_verify_comb_wide(VerifyArgs a, CombArgs
       if (flags_ok && eq) atomicOr(reinterpret_cast<unsigned long long*>(a.out_bits) + (i >> 6), 1ull << (i & 63));
     }
   }
+}
+
+__global__ __launch_bounds__(128) void k_verify_comb_wide(VerifyArgs a, CombArgs ca) {
+  __shared__ fe sh_rx, sh_ry;
+  __shared__ int sh_rok;
+  const uint64_t i = blockIdx.x;
+  if (i >= a.n) return;   // block-uniform
+  verify_wide_body(a, ca, ca.vbytes, i, a.strict, sh_rx, sh_ry, sh_rok);
+}
+
+// The cached equations of a group (GroupArgs above): a.committee is the cache that holds their keys
+// (the committee cache or the auto key cache); ca.comb_base as k_verify_comb_wide's.
+__global__ __launch_bounds__(128) void k_verify_group_wide(VerifyArgs a, CombArgs ca, GroupArgs g) {
+  __shared__ fe sh_rx, sh_ry;
+  __shared__ int sh_rok;
+  uint64_t i;
+  int mode;
+  if (!group_equation(a, g, i, mode)) return;
+  verify_wide_body(a, ca, g.vbytes, i, mode, sh_rx, sh_ry, sh_rok);
 }
 
 // ------------------------------------------------------------------------------- certificates

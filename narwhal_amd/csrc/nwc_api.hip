@@ -290,6 +290,7 @@ struct Carve {
 
 uint32_t auto_keys_cap();
 void signers_shutdown();
+void verifiers_shutdown();
 int auto_grow(DevCtx& d, uint32_t ncap);
 bool comb16_enabled();
 
@@ -2043,6 +2044,7 @@ int nwc_init(uint32_t device_mask) {
 void nwc_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_mu);
   signers_shutdown();   // live signers' key records are zeroed and freed first
+  verifiers_shutdown();  // live verifiers finish what is queued; their pinned group buffers go
   for (auto& d : g_devs) {
     std::lock_guard<std::mutex> dl(d->mu);
     (void)hipSetDevice(d->hip_id);
@@ -3115,6 +3117,7 @@ int nwc_dev_sanitize_messages(const void* d_data, const void* d_offsets, uint64_
 
 #include "digester.h"
 #include "signer.h"
+#include "verifier.h"
 
 extern "C" {
 

@@ -55,6 +55,12 @@ extern "C" {
     pub fn nwc_dev_sign(signer: *mut c_void, d_msgs: *const c_void, msg_stride: u64, n: u64, d_sigs: *mut c_void,
                         stream: *mut c_void) -> c_int;
     pub fn nwc_signer_destroy(signer: *mut c_void) -> c_int;
+    pub fn nwc_verifier_create(max_requests: u32, max_wait_us: u32) -> *mut c_void;
+    pub fn nwc_verifier_verify_strict(verifier: *mut c_void, msg32: *const u8, pk: *const u8, sig: *const u8) -> c_int;
+    pub fn nwc_verifier_verify_batch(verifier: *mut c_void, msg32: *const u8, pks: *const u8, sigs: *const u8, n: usize,
+                                     bad_bitmap: *mut u8) -> c_int;
+    pub fn nwc_verifier_stats(verifier: *mut c_void, out: *mut u64) -> c_int;
+    pub fn nwc_verifier_destroy(verifier: *mut c_void) -> c_int;
     pub fn nwc_set_committee(pks: *const u8, n: usize) -> c_int;
     pub fn nwc_cache_stats(committee_keys: *mut u32, auto_keys: *mut u32) -> c_int;
     pub fn nwc_auto_cache_info(capacity: *mut u32, builds: *mut u64, hits: *mut u64) -> c_int;

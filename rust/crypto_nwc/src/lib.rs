@@ -241,3 +241,68 @@ impl Drop for Signer {
         unsafe { ffi::nwc_signer_destroy(self.h) };
     }
 }
+
+/// Concurrent `Signature::verify` / `verify_batch` calls behind shared launches (`nwc_verifier`):
+/// tokio tasks that verify at the same time (node/src/main.rs:17, worker/src/worker.rs:182,227)
+/// call one process-wide `Verifier`; requests that arrive together share a launch and each caller
+/// returns when its own verdicts are in.  Same verdicts as `verify_strict` / `verify_batch`.
+pub struct Verifier {
+    h: *mut std::os::raw::c_void,
+}
+
+unsafe impl Send for Verifier {}
+unsafe impl Sync for Verifier {}   // every call on a verifier may be made from any number of threads
+
+/// Counters of a `Verifier` (`nwc_verifier_stats_t`).
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct VerifierStats {
+    pub groups: u64,
+    pub requests: u64,
+    pub equations: u64,
+    pub wide_equations: u64,
+    pub cold_equations: u64,
+    pub redone_equations: u64,
+    pub bypassed_requests: u64,
+    pub max_requests_in_group: u64,
+}
+
+impl Verifier {
+    /// A group closes at `max_requests` requests (0 = as many as fit) or `max_wait_us` after its
+    /// first request (0 = never wait for company).  Panics on a device failure.
+    pub fn new(max_requests: u32, max_wait_us: u32) -> Self {
+        init(0);
+        let h = unsafe { ffi::nwc_verifier_create(max_requests, max_wait_us) };
+        if h.is_null() {
+            let msg = unsafe { CStr::from_ptr(ffi::nwc_last_error()) };
+            panic!("libnwc verifier: {}", msg.to_string_lossy());
+        }
+        Verifier { h }
+    }
+
+    /// `Signature::verify` = dalek `verify_strict`.
+    pub fn verify(&self, digest: &[u8; 32], public_key: &[u8; 32], signature: &[u8; 64]) -> bool {
+        check(unsafe { ffi::nwc_verifier_verify_strict(self.h, digest.as_ptr(), public_key.as_ptr(), signature.as_ptr()) })
+    }
+
+    /// `Signature::verify_batch` over one digest.  An empty batch is valid.
+    pub fn verify_batch(&self, digest: &[u8; 32], public_keys: &[[u8; 32]], signatures: &[[u8; 64]]) -> bool {
+        assert_eq!(public_keys.len(), signatures.len());
+        check(unsafe {
+            ffi::nwc_verifier_verify_batch(self.h, digest.as_ptr(), public_keys.as_ptr() as *const u8,
+                                           signatures.as_ptr() as *const u8, public_keys.len(), std::ptr::null_mut())
+        })
+    }
+
+    pub fn stats(&self) -> VerifierStats {
+        let mut s = VerifierStats::default();
+        check(unsafe { ffi::nwc_verifier_stats(self.h, &mut s as *mut VerifierStats as *mut u64) });
+        s
+    }
+}
+
+impl Drop for Verifier {
+    fn drop(&mut self) {
+        unsafe { ffi::nwc_verifier_destroy(self.h) };
+    }
+}
