@@ -31,8 +31,18 @@
 #include "kernels.hip"
 #include "launch_keys.h"
 #include "messages.h"
+#include "verify_plan.h"
 
 namespace {
+
+using nwc::plan::settings;
+using nwc::plan::VPath;
+using nwc::plan::LV_ALL_CACHED;
+using nwc::plan::LV_OUT_ZEROED;
+using nwc::plan::LV_AUTO;
+using nwc::plan::LV_STAMP;
+using nwc::plan::LV_DEFER_LIST;
+static_assert(nwc::plan::LK_MIN_EQUATIONS == nwc::LK_MIN_EQUATIONS, "verify_plan.h routes by launch_keys.h's threshold");
 
 thread_local std::string t_err;
 thread_local int t_dev = 0;
@@ -240,30 +250,13 @@ struct DevCtx {
 #define NWC_COMB_MAX_KEYS 1024
 #endif
 
-// batches up to this size take the latency kernel (k_verify_comb_wide) on the comb path
-// Host calls of at least 2 chunks are pipelined: chunk i+1's inputs cross PCIe while chunk i
-// verifies.  A chunk is one full round of resident lanes (2 blocks of 256 per CU x 256 CUs).
-#ifndef NWC_HOST_CHUNK
-#define NWC_HOST_CHUNK (1u << 17)
-#endif
-#ifndef NWC_HOST_CHUNK_MAX
-#define NWC_HOST_CHUNK_MAX (1u << 20)
-#endif
-#ifndef NWC_MSG_CHUNK
-#define NWC_MSG_CHUNK (24u << 20)   // largest pipelined chunk of nwc_sanitize_messages, bytes of wire messages (A/B: profiles/r05/wire_host.md)
-#endif
-#ifndef NWC_HOST_CHUNK_GROWTH
-#define NWC_HOST_CHUNK_GROWTH 3
-#endif
+// (the switches' compile-time defaults, NWC_WIDE_MAX among them, are in verify_plan.h)
 #ifndef NWC_PINNED_STAGE_MAX
 #define NWC_PINNED_STAGE_MAX (1u << 20)
 #endif
 // persistent verify grid: this many blocks per resident block slot
 #ifndef NWC_VERIFY_GRID_MULT
 #define NWC_VERIFY_GRID_MULT 8
-#endif
-#ifndef NWC_WIDE_MAX
-#define NWC_WIDE_MAX 1024
 #endif
 
 std::mutex g_mu;
@@ -288,13 +281,11 @@ struct Carve {
   template <class T> T* take(size_t bytes) { T* p = reinterpret_cast<T*>(base + off); off += align256(bytes); return p; }
 };
 
-uint32_t auto_keys_cap();
 void signers_shutdown();
 void verifiers_shutdown();
 int auto_grow(DevCtx& d, uint32_t ncap);
-bool comb16_enabled();
 
-// Test and A/B knobs settable at run time (nwc_diag_set), defaults from the environment read once:
+// Test and A/B knobs settable at run time (nwc_diag_set), defaults from the environment (settings()):
 // NWC_STRAUS_NQ (votes per Straus sub-batch, 12) and NWC_FORCE_WINDOWS (half-ladder window count
 // forced on every wave, 0 = off).  Atomics: a setter racing a launch gives that launch either value.
 struct Knobs {
@@ -306,11 +297,12 @@ struct Knobs {
   std::atomic<uint32_t> sign_path{0};     // tests: 0 = by size (NWC_SIGN_WIDE_MAX), 1 = k_sign, 2 = k_sign_wide
   std::atomic<uint64_t> dalek_seed{0};    // tests: fixed seed of the per-certificate equation's z_i (0 = host CSPRNG)
   Knobs() {
-    if (const char* e = std::getenv("NWC_LAUNCH_KEYS")) launch_keys = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("NWC_STRAUS_NQ")) straus_nq = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("NWC_FORCE_WINDOWS")) force_windows = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("NWC_MSM_GROUP")) msm_group = (uint32_t)std::strtoul(e, nullptr, 10);
-    if (const char* e = std::getenv("NWC_MSM_ADAPT")) msm_adapt = std::atoi(e) != 0;
+    const nwc::plan::Settings& s = settings();
+    launch_keys = s.launch_keys;
+    straus_nq = s.straus_nq;
+    force_windows = s.force_windows;
+    msm_group = s.msm_group;
+    msm_adapt = s.msm_adapt;
   }
 };
 Knobs& knobs() {
@@ -355,7 +347,7 @@ int ensure_verify_tables(DevCtx& d) {
   hipLaunchKernelGGL(nwc::k_build_comb<nwc::BaseComb>, dim3((unsigned)((nwc::BaseComb::per + 255) / 256)), dim3(256), 0, d.stream,
                      (const nwc::u32*)nullptr, 1u, d.comb_base);
   HIP_TRY(hipGetLastError());
-  if (comb16_enabled()) {
+  if (settings().comb16) {
     // radix-2^22 basepoint comb (3.2 GB): the committee comb kernel and the cold kernel's s B
     HIP_TRY(hipMalloc(&d.comb16, nwc::COMB16_TOTAL * sizeof(nwc::ge_niels_pad)));
     HIP_TRY(hipMalloc(&d.comb16_bases, nwc::COMB16_WINDOWS * sizeof(nwc::ge_p3)));
@@ -382,7 +374,7 @@ int ensure_verify_tables(DevCtx& d) {
   // auto key cache: the first AUTO_INIT_KEYS keys' arrays (~330 MB), their slot table and the key
   // comb builder's scratch are allocated here, so the call that first fills the cache only
   // queues its build (growth beyond this is stream-ordered, auto_grow)
-  if (const uint32_t acap = auto_keys_cap()) {
+  if (const uint32_t acap = settings().auto_keys) {
     if (int rc = auto_grow(d, std::min<uint32_t>(acap, 16u))) return rc;
     d.ak_slot_cap = 64;
     while (d.ak_slot_cap < 8 * std::min<uint32_t>(acap, 16u)) d.ak_slot_cap <<= 1;
@@ -426,26 +418,6 @@ int build_key_combs(DevCtx& d, const nwc::u32* keys, uint32_t m, nwc::ge_niels_p
                      (const nwc::ge_p3*)d.kb_bases, 0u, m, (const uint32_t*)nullptr, out);
   HIP_TRY(hipGetLastError());
   return 0;
-}
-
-// NWC_AUTO_KEYS: capacity of the per-device auto key cache (default 256 keys, 20 MB of combs
-// each, allocated on first use; 0 disables it).
-uint32_t auto_keys_cap() {
-  static const uint32_t cap = [] {
-    const char* e = std::getenv("NWC_AUTO_KEYS");
-    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 256u;
-  }();
-  return cap;
-}
-// NWC_COMB16=0: no radix-2^22 basepoint comb at nwc_init (saves 3.2 GB of HBM per device);
-// committee batches then take the cached ladder (k_verify<true, true>) instead of the comb
-// kernel, and first-sight small calls the one-lane path instead of the cold kernel.
-bool comb16_enabled() {
-  static const bool on = [] {
-    const char* e = std::getenv("NWC_COMB16");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
 }
 
 constexpr size_t AUTO_SEEN_MAX = 4096;   // keys remembered as seen once (cleared when full)
@@ -499,7 +471,7 @@ void auto_reset(DevCtx& d) {
 // updated once the build is enqueued; the call does not wait for it (its copy sources stay in
 // d.ak_pend_* until the next build has synchronised).  Caller holds d.mu and has set the device.
 int auto_insert(DevCtx& d, const uint8_t* pks, uint64_t n) {
-  const uint32_t cap = auto_keys_cap();
+  const uint32_t cap = settings().auto_keys;
   if (cap == 0) return 0;
   std::vector<nwc::u32> add;
   std::unordered_set<std::string> added;
@@ -573,45 +545,12 @@ int auto_insert(DevCtx& d, const uint8_t* pks, uint64_t n) {
 }
 
 // ---- launch helpers (caller holds the device mutex and has set the device) -----------------
-// Verification path (NWC_VERIFY_PATH): default = the doubling-free comb kernel for equations whose
-// key is in the committee cache (when the committee has combs) and half-size equations with
-// full-length fallback for the rest; "half" = no comb kernel; "full" = the full-length ladder for
-// every lane.  The alternatives exist to cross-check the paths against each other.
-enum class VPath { Default, Half, Full };
-VPath verify_path() {
-  static const VPath p = [] {
-    const char* e = std::getenv("NWC_VERIFY_PATH");
-    if (e && std::strcmp(e, "full") == 0) return VPath::Full;
-    if (e && std::strcmp(e, "half") == 0) return VPath::Half;
-    return VPath::Default;
-  }();
-  return p;
-}
-
 // Device memory of the verification path (a primary and workers share the GPU:
 // worker/src/worker.rs:182,227).  One launch takes at most NWC_VERIFY_MAX_LAUNCH equations (larger
 // calls run as consecutive launches of that size, launch_verify), so the per-launch lists below are
 // bounded; and lists larger than NWC_VERIFY_KEEP_BYTES are shrunk to a smaller launch's size
 // when one comes (after the device has finished with them).  The per-lane table slots are sized
 // for the resident grid, not for n.
-#ifndef NWC_VERIFY_MAX_LAUNCH
-#define NWC_VERIFY_MAX_LAUNCH (16ull << 20)
-#endif
-uint64_t verify_max_launch() {
-  static const uint64_t m = [] {
-    const char* e = std::getenv("NWC_VERIFY_MAX_LAUNCH");
-    const uint64_t v = e ? std::strtoull(e, nullptr, 10) : (uint64_t)NWC_VERIFY_MAX_LAUNCH;
-    return std::max<uint64_t>(1u << 16, v / 64 * 64);
-  }();
-  return m;
-}
-size_t verify_keep_bytes() {
-  static const size_t k = [] {
-    const char* e = std::getenv("NWC_VERIFY_KEEP_BYTES");
-    return e ? (size_t)std::strtoull(e, nullptr, 10) : (size_t)256 << 20;
-  }();
-  return k;
-}
 // bytes of the per-launch lists: fb_list, uc_list, ts_uniq (4 B per entry) and the torsion hash set
 size_t list_bytes(uint64_t cap, uint64_t slots) { return 12 * (size_t)cap + 8 * (size_t)slots; }
 void free_lists(DevCtx& d) {
@@ -628,7 +567,7 @@ void free_lists(DevCtx& d) {
 
 int ensure_scratch(DevCtx& d, size_t bytes, uint64_t n) {
   const uint64_t want = n + n / 2 + 4096;
-  const bool shrink = !d.hold_lists && d.fb_cap > 4 * want && list_bytes(d.fb_cap, d.ts_slot_count) > verify_keep_bytes();
+  const bool shrink = !d.hold_lists && d.fb_cap > 4 * want && list_bytes(d.fb_cap, d.ts_slot_count) > settings().verify_keep_bytes;
   if (bytes <= d.scratch_cap && n <= d.fb_cap && !shrink) return 0;
   HIP_TRY(hipEventSynchronize(d.scratch_free));
   if (bytes > d.scratch_cap) {
@@ -653,6 +592,31 @@ int ensure_scratch(DevCtx& d, size_t bytes, uint64_t n) {
     d.fb_cap = c;
   }
   if (!d.ts_nuniq) HIP_TRY(hipMalloc(&d.ts_nuniq, sizeof(uint32_t)));
+  return 0;
+}
+
+// ev grown to n events (one per chunk in flight, created on first use)
+int ensure_events(std::vector<hipEvent_t>& ev, size_t n) {
+  while (ev.size() < n) {
+    hipEvent_t e;
+    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    ev.push_back(e);
+  }
+  return 0;
+}
+
+// Replaces the device buffer p by one of need + headroom bytes, once its users have finished: every
+// launch that uses these buffers records scratch_free after its last kernel, so waiting for it
+// (and for *drain, a stream whose queued work may use p as well; nullptr = none) drains them on
+// any stream.
+int regrow(DevCtx& d, uint8_t*& p, size_t& cap, size_t need, const hipStream_t* drain, size_t headroom) {
+  HIP_TRY(hipEventSynchronize(d.scratch_free));
+  if (drain) HIP_TRY(hipStreamSynchronize(*drain));
+  if (p) HIP_TRY(hipFree(p));
+  p = nullptr;
+  cap = 0;
+  HIP_TRY(hipMalloc(&p, need + headroom));
+  cap = need + headroom;
   return 0;
 }
 
@@ -689,29 +653,6 @@ int launch_torsion(DevCtx& d, const uint8_t* pks, uint64_t* out_words, uint64_t 
     HIP_TRY(hipGetLastError());
   }
   return 0;
-}
-
-// NWC_COLD=0: small uncached calls take k_verify (one lane per equation) instead of the
-// limb-sliced k_verify_cold (A/B and tests)
-bool cold_path() {
-  static const bool on = [] {
-    const char* e = std::getenv("NWC_COLD");
-    return !(e && std::strcmp(e, "0") == 0) && comb16_enabled();   // its s B is a comb16 sum
-  }();
-  return on;
-}
-
-// largest launch the cold kernel takes (one 4-wave block per equation); above it the one-lane
-// ladder's throughput wins (tools/cold_sizes.py)
-#ifndef NWC_COLD_MAX
-#define NWC_COLD_MAX 3072
-#endif
-uint64_t cold_max() {
-  static const uint64_t m = [] {
-    const char* e = std::getenv("NWC_COLD_MAX");   // A/B
-    return e ? (uint64_t)std::strtoull(e, nullptr, 10) : (uint64_t)NWC_COLD_MAX;
-  }();
-  return m;
 }
 
 // Device buffers of the launch keys (launch_keys.h), allocated once per device except the combs
@@ -776,25 +717,12 @@ int lk_reserve(DevCtx& d, const uint8_t* pks, uint64_t n, hipStream_t s) {
 // Large host calls copy their pageable inputs through the device's pinned stages, filled by
 // NWC_HOST_STAGING_THREADS (8) host threads (straight from pageable memory measured 7-10 % slower,
 // profiles/r05/wire_host.md; that switch was removed in round 6).
-// NWC_HOST_TIMING: per-phase times of large host calls on stderr (diagnostics)
-bool host_timing() {
-  static const bool on = std::getenv("NWC_HOST_TIMING") != nullptr;
-  return on;
-}
-unsigned stager_threads() {
-  static const unsigned t = [] {
-    const char* e = std::getenv("NWC_HOST_STAGING_THREADS");
-    return e ? (unsigned)std::max(1, std::atoi(e)) : 8u;
-  }();
-  return t;
-}
-
 // The device's transfer stream and its pinned stages.  Caller holds d.mu.
 int ensure_stager(DevCtx& d) {
   if (!d.xfer) HIP_TRY(hipStreamCreateWithFlags(&d.xfer, hipStreamNonBlocking));
   if (!d.stager) {
     auto st = std::make_unique<HostStager>();
-    const hipError_t e = st->init(d.xfer, stager_threads());
+    const hipError_t e = st->init(d.xfer, settings().host_staging_threads);
     if (e != hipSuccess) {
       st->release();
       return set_err(NWC_ERR_DEVICE, "host stager: %s", hipGetErrorString(e));
@@ -809,7 +737,7 @@ int ensure_stager(DevCtx& d) {
 // used them, each of which records scratch_free -- so a process that ran the Straus or MSM entry
 // once holds at most the keep threshold of them while it verifies by other paths.
 int release_idle_buffers(DevCtx& d, const uint8_t* in_use) {
-  const size_t keep = verify_keep_bytes();
+  const size_t keep = settings().verify_keep_bytes;
   struct Buf { uint8_t** p; size_t* cap; } bufs[] = {
       {&d.straus_scratch, &d.straus_cap}, {&d.msm_scratch, &d.msm_cap}, {&d.rs_buf, &d.rs_cap},
       {&d.pair_buf, &d.pair_cap}, {&d.sign_buf, &d.sign_cap}};
@@ -828,18 +756,7 @@ int release_idle_buffers(DevCtx& d, const uint8_t* in_use) {
   return 0;
 }
 
-// launch_verify flags: the caller checked on the host that every key is in the committee cache,
-// and/or out_words is already zero (both let the latency path run as a single kernel)
-// LV_AUTO: the keys are in the auto cache; LV_STAMP: the headline kernel's clock-stamp build
-// (k_verify<.., STAMP>, nwc_diag_verify_clock)
-// LV_DEFER_LIST: a launch on the committee-cache comb path (deferrable_list()) that only appends
-// its uncached equations, as list_base + i, to the call-wide list; the caller zeroed the list's
-// count and sized the lists (ensure_scratch) for the whole call before the first such launch, and
-// runs the list, fallback and torsion passes once over all of them (finish_deferred_list).  The
-// chunked sanitize pipeline: one set of those small launches per call instead of per chunk.
-constexpr int LV_ALL_CACHED = 1, LV_OUT_ZEROED = 2, LV_AUTO = 4, LV_STAMP = 8, LV_DEFER_LIST = 16;
-
-// One launch of the paired strict host pipeline (verify_range): launches on two streams may run at
+// One launch of the paired strict host pipeline (verify_paired): launches on two streams may run at
 // the same time, so each takes half of the table slots (`half`; grid capped at half the persistent
 // grid) and lists its failed reductions in its own region of the fallback list with its own count;
 // the caller orders the slots against other launches (scratch_free), sized the list beforehand and
@@ -851,232 +768,235 @@ struct PairLaunch {
   uint32_t* fb_count;
 };
 
-// launch_verify's comb path over the committee cache for any n (what LV_DEFER_LIST needs)
-bool deferrable_list(const DevCtx& d) {
-  return verify_path() == VPath::Default && d.cm_n && d.cm_comb && d.comb16;
+// The committee cache, the auto cache and the launch keys as a kernel's key set.
+nwc::Committee committee_of(const DevCtx& d) {
+  return nwc::Committee{d.cm_keys, d.cm_flags, d.cm_tables, d.cm_comb, d.cm_slots, d.cm_slot_mask, d.cm_n};
+}
+nwc::Committee auto_committee_of(const DevCtx& d) {
+  return nwc::Committee{d.ak_keys, d.ak_flags, d.ak_tables, d.ak_comb, d.ak_slots, d.ak_host.mask, d.ak_n};
+}
+nwc::Committee launch_committee_of(const DevCtx& d) {
+  return nwc::Committee{d.lk.keys, d.lk.flags, nullptr, d.lk.comb, d.lk.slots, nwc::LK_SLOTS - 1, nwc::LK_MAX_KEYS};
 }
 
-// NWC_FORCE_FALLBACK_EVERY: test hook, every k-th equation of the half-size kernels takes the fallback
-uint32_t force_fallback_every() {
-  static const uint32_t v = [] {
-    const char* e = std::getenv("NWC_FORCE_FALLBACK_EVERY");
-    return e ? (uint32_t)std::strtoul(e, nullptr, 10) : 0u;
-  }();
+// What verify_plan.h's decisions read of the device, the settings and the knobs.
+nwc::plan::DeviceView device_view(const DevCtx& d) {
+  const nwc::plan::Settings& st = settings();
+  nwc::plan::DeviceView v;
+  v.path = st.verify_path;
+  v.cm_n = d.cm_n;
+  v.cm_comb = d.cm_comb != nullptr;
+  v.comb16 = d.comb16 != nullptr;
+  v.ak_n = d.ak_n;
+  v.ak_comb = d.ak_comb != nullptr;
+  v.launch_keys = knobs().launch_keys.load() != 0;
+  v.cold = st.cold;
+  v.cold_max = st.cold_max;
+  v.fb_cap = d.fb_cap;
+  v.verify_max_launch = st.verify_max_launch;
   return v;
 }
+bool deferrable_list(const DevCtx& d) { return nwc::plan::deferrable_list(device_view(d)); }
+// Whether launch_verify takes the comb path (k_verify_comb) for a plain launch of n equations.
+bool takes_comb_path(const DevCtx& d, uint64_t n, int strict) {
+  return nwc::plan::comb_path(device_view(d), n, strict != 0).comb;
+}
 
-int launch_verify(DevCtx& d, const uint8_t* msgs, const uint32_t* msg_index, uint64_t msg_stride,
-                  const uint8_t* pks, const uint8_t* sigs, uint64_t n, int strict, uint64_t* out_words,
-                  hipStream_t s, int flags = 0, uint8_t* vbytes = nullptr, uint64_t list_base = 0,
-                  const PairLaunch* pl = nullptr, const nwc::SignRecs* sr = nullptr,
-                  const nwc::SignPass* sp = nullptr) {
-  if (n == 0) return 0;
-  if (int rc = ensure_verify_tables(d)) return rc;
-  if (int rc = release_idle_buffers(d, nullptr)) return rc;
-  if (n > verify_max_launch() && !vbytes) {
-    // consecutive launches of at most NWC_VERIFY_MAX_LAUNCH equations (a multiple of 64: whole
-    // verdict words), so the per-launch lists stay bounded; every equation is independent, so the
-    // verdicts are those of one launch (launch keys and the torsion set are per launch anyway)
-    const uint64_t step = verify_max_launch();
-    for (uint64_t lo = 0; lo < n; lo += step) {
-      const uint64_t len = std::min(step, n - lo);
-      if (int rc = launch_verify(d, msg_index ? msgs : msgs + 32 * lo * msg_stride, msg_index ? msg_index + lo : nullptr,
-                                 msg_stride, pks + 32 * lo, sigs + 64 * lo, len, strict, out_words + lo / 64, s, flags,
-                                 nullptr, list_base + lo))
-        return rc;
-    }
-    return 0;
+// One verification launch: equation i checks msgs (msg_index[i] or i * msg_stride), pks and sigs on
+// the device and sets bit i of out_words, on `stream`.
+struct VerifyLaunch {
+  const uint8_t* msgs = nullptr;
+  const uint32_t* msg_index = nullptr;
+  uint64_t msg_stride = 0;
+  const uint8_t* pks = nullptr;
+  const uint8_t* sigs = nullptr;
+  uint64_t n = 0;
+  int strict = 0;
+  uint64_t* out_words = nullptr;
+  hipStream_t stream = nullptr;
+  int flags = 0;                            // LV_*
+  uint8_t* vbytes = nullptr;                // zero-copy: a verdict byte per equation in host memory
+  uint64_t list_base = 0;                   // LV_DEFER_LIST: equation i is listed as list_base + i
+  const PairLaunch* pair = nullptr;
+  const nwc::SignRecs* sign_recs = nullptr;   // the sign tests deferred: their records
+  const nwc::SignPass* sign_pass = nullptr;   // ... and the previous launch's votes, tested in this launch's first blocks
+};
+
+// The single-kernel launches (latency kernels, zero-copy cold): no table slots, no lists.
+int enqueue_single(DevCtx& d, const VerifyLaunch& q, const nwc::plan::Route& r) {
+  using nwc::plan::Kernel;
+  const uint64_t n = q.n;
+  const bool cold = r.kernel == Kernel::ZeroCopyCold;
+  if (r.kernel == Kernel::AutoWide) ++d.ak_hits;
+  const nwc::Committee cm = cold ? nwc::Committee{} : r.kernel == Kernel::AutoWide ? auto_committee_of(d) : committee_of(d);
+  const nwc::VerifyArgs a{q.msgs, q.msg_index, q.msg_stride, q.pks, q.sigs, q.out_words, n, q.strict, d.base_table, d.base24,
+                          d.scratch, d.fb_list, d.fb_count, cold ? settings().force_fallback_every : 0u, cm};
+  if (r.zero_words) HIP_TRY(hipMemsetAsync(q.out_words, 0, 8 * r.zero_words, q.stream));
+  if (cold) {
+    hipLaunchKernelGGL(nwc::k_verify_cold, dim3((unsigned)n), dim3(256), 0, q.stream, a, (const nwc::ge_niels_pad*)d.comb16,
+                       q.vbytes);
+  } else {
+    // a key missing on the device after all sets the word after the verdict words
+    const nwc::CombArgs ca{nullptr, reinterpret_cast<uint32_t*>(q.out_words + (n + 63) / 64), d.comb_base, d.comb16,
+                           q.vbytes};
+    hipLaunchKernelGGL(nwc::k_verify_comb_wide, dim3((unsigned)n), dim3(128), 0, q.stream, a, ca);
   }
-  // equation indices travel as uint32 (fallback / uncached / torsion lists)
-  if (n > 0xFFFFFFFFull) return set_err(NWC_ERR_ARG, "more than 2^32 - 1 equations in one launch");
-  const VPath path = verify_path();
-  if ((flags & LV_AUTO) && (flags & LV_ALL_CACHED) && path == VPath::Default && n <= NWC_WIDE_MAX && d.ak_n) {
-    // latency path over the auto key cache (same kernel, the auto cache as its committee)
-    ++d.ak_hits;
-    const nwc::Committee cm{d.ak_keys, d.ak_flags, d.ak_tables, d.ak_comb, d.ak_slots, d.ak_host.mask, d.ak_n};
-    const nwc::VerifyArgs a{msgs, msg_index, msg_stride, pks, sigs, out_words, n, strict, d.base_table, d.base24,
-                            d.scratch, d.fb_list, d.fb_count, 0u, cm};
-    const nwc::CombArgs ca{nullptr, reinterpret_cast<uint32_t*>(out_words + (n + 63) / 64), d.comb_base, d.comb16,
-                           vbytes};
-    if (!vbytes && !(flags & LV_OUT_ZEROED)) HIP_TRY(hipMemsetAsync(out_words, 0, 8 * ((n + 63) / 64 + 1), s));
-    hipLaunchKernelGGL(nwc::k_verify_comb_wide, dim3((unsigned)n), dim3(128), 0, s, a, ca);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  const uint32_t force_every = force_fallback_every();
-  if (vbytes && !(flags & LV_ALL_CACHED)) {
-    // zero-copy cold launch (the caller checked: no committee cache, n <= NWC_WIDE_MAX, default
-    // path, cold kernel on): no scratch, no fallback launch, verdict bytes straight to the host
-    const nwc::VerifyArgs a{msgs, msg_index, msg_stride, pks, sigs, out_words, n, strict, d.base_table, d.base24,
-                            d.scratch, d.fb_list, d.fb_count, force_every, nwc::Committee{}};
-    hipLaunchKernelGGL(nwc::k_verify_cold, dim3((unsigned)n), dim3(256), 0, s, a, (const nwc::ge_niels_pad*)d.comb16, vbytes);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
-  // (the throughput comb kernel needs the basepoint comb16; the latency kernel does not)
-  // A large batch-leaf launch without a committee cache brings its own committee: the keys it
-  // repeats join the launch-key set and its votes take the comb kernel (launch_keys.h).
-  const bool lk = path == VPath::Default && !strict && !d.cm_n && d.comb16 && n >= nwc::LK_MIN_EQUATIONS &&
-                  knobs().launch_keys.load() && !(flags & LV_AUTO);
-  const bool comb = lk || (path == VPath::Default && d.cm_n && d.cm_comb && (n <= NWC_WIDE_MAX || d.comb16));
-  const bool defer = (flags & LV_DEFER_LIST) != 0;
-  if (defer && (lk || !comb || list_base + n > d.fb_cap || !deferrable_list(d)))
-    return set_err(NWC_ERR_ARG, "deferred list launch off the committee-cache comb path");
-  if (sr && (!comb || (defer && (list_base & 63))))
-    return set_err(NWC_ERR_ARG, "sign-deferred launch off the comb path or off a verdict word");
-  if (comb && n <= NWC_WIDE_MAX && (flags & LV_ALL_CACHED)) {
-    // latency path, one launch: no scratch, no uncached list, no fallback (the comb path has none).
-    // The host checked every key against its view of the cache (set under g_cm_mu, like the
-    // devices'); should a key still be missing on the device, the kernel sets the word after the
-    // verdict words instead of listing it, and the caller re-runs the general path.
-    const nwc::Committee cm{d.cm_keys, d.cm_flags, d.cm_tables, d.cm_comb, d.cm_slots, d.cm_slot_mask, d.cm_n};
-    const nwc::VerifyArgs a{msgs, msg_index, msg_stride, pks, sigs, out_words, n, strict, d.base_table, d.base24,
-                            d.scratch, d.fb_list, d.fb_count, 0u, cm};
-    const nwc::CombArgs ca{nullptr, reinterpret_cast<uint32_t*>(out_words + (n + 63) / 64), d.comb_base, d.comb16,
-                           vbytes};
-    if (!vbytes && !(flags & LV_OUT_ZEROED)) HIP_TRY(hipMemsetAsync(out_words, 0, 8 * ((n + 63) / 64 + 1), s));
-    hipLaunchKernelGGL(nwc::k_verify_comb_wide, dim3((unsigned)n), dim3(128), 0, s, a, ca);
-    HIP_TRY(hipGetLastError());
-    return 0;
-  }
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// The launches over the table slots and lists, as the route says: the launch-key build, the
+// torsion test beside, the main kernel, the uncached list's pass, the fallback, the torsion pass.
+int enqueue_listed(DevCtx& d, const VerifyLaunch& q, const nwc::plan::Route& r) {
+  using nwc::plan::Kernel;
+  using nwc::plan::Torsion;
+  const uint64_t n = q.n;
+  const hipStream_t s = q.stream;
+  const bool defer = (q.flags & LV_DEFER_LIST) != 0;
   const uint64_t tiles = (n + 255) / 256;
   // persistent grid: a few blocks per resident slot so the tail is short
   const uint64_t cap = (uint64_t)d.cus * d.verify_blocks_per_cu * NWC_VERIFY_GRID_MULT;
   size_t need = (size_t)cap * 256 * 2 * nwc::TAB_BYTES_PER_LANE;
-  const bool pair = pl != nullptr;
-  const uint64_t gcap = pair ? cap / 2 : cap;
+  const uint64_t gcap = q.pair ? cap / 2 : cap;
   const unsigned grid = (unsigned)(tiles < gcap ? tiles : gcap);
   // comb grid: at most the resident blocks; tile t goes to block t mod grid, so every lane gets
   // ceil or floor of n / lanes equations (in chunks of COMB_BATCH sharing one inversion), and
   // a small n spreads one equation per lane
   unsigned gridc = 0;
-  if (comb) {
+  if (r.comb) {
     const uint64_t resident = (uint64_t)d.cus * d.comb_blocks_per_cu;
     gridc = (unsigned)std::min<uint64_t>(tiles, resident);
     need = std::max(need, (size_t)resident * 256 * nwc::COMB_BYTES_PER_LANE);
   }
   // (deferred: n = the lists' capacity, so they are neither grown nor shrunk under the pending list)
   if (int rc = ensure_scratch(d, need, defer ? d.fb_cap : n)) return rc;
-  if (lk)
+  if (r.lk_build)
     if (int rc = lk_ensure(d, s)) return rc;
-  if (pair && (!strict || comb || path == VPath::Full || d.cm_n))
-    return set_err(NWC_ERR_ARG, "paired launch off the strict half-size path");
-  if (!pair) HIP_TRY(hipStreamWaitEvent(s, d.scratch_free, 0));
-  if (lk) {
+  if (r.error) return set_err(NWC_ERR_ARG, "%s", r.error);
+  if (r.scratch_order) HIP_TRY(hipStreamWaitEvent(s, d.scratch_free, 0));
+  if (r.lk_build) {
     // the set's update is ordered after every launch that read it (scratch_free) and before this
     // launch's comb kernel; the builds exit at once when no key joined
-    if (int rc = lk_reserve(d, pks, n, s)) return rc;
-    hipLaunchKernelGGL(nwc::k_lk_select, dim3(1), dim3(1024), 0, s, pks, n, d.lk);
+    if (int rc = lk_reserve(d, q.pks, n, s)) return rc;
+    hipLaunchKernelGGL(nwc::k_lk_select, dim3(1), dim3(1024), 0, s, q.pks, n, d.lk);
     hipLaunchKernelGGL(nwc::k_lk_keys, dim3((nwc::LK_MAX_KEYS + 63) / 64), dim3(64), 0, s, d.lk);
     hipLaunchKernelGGL(nwc::k_build_comb_from_bases<nwc::KeyComb>, dim3((unsigned)(d.cus * 8)), dim3(256), 0, s,
                        (const nwc::ge_p3*)d.lk.bases, 0u, 0u, (const uint32_t*)d.lk.state, d.lk.comb);
     HIP_TRY(hipGetLastError());
   }
-  const nwc::Committee cm = lk ? nwc::Committee{d.lk.keys, d.lk.flags, nullptr, d.lk.comb, d.lk.slots, nwc::LK_SLOTS - 1,
-                                                nwc::LK_MAX_KEYS}
-                               : nwc::Committee{d.cm_keys, d.cm_flags, d.cm_tables, d.cm_comb, d.cm_slots, d.cm_slot_mask, d.cm_n};
-  nwc::VerifyArgs a{msgs, msg_index, msg_stride, pks, sigs, out_words, n, strict, d.base_table, d.base24, d.scratch,
-                    d.fb_list, d.fb_count, force_every, cm};
-  if (pair) {
-    a.scratch = d.scratch + (size_t)(pl->half ? cap / 2 : 0) * 256 * 2 * nwc::TAB_BYTES_PER_LANE;
-    a.fb_list = pl->fb_list;
-    a.fb_count = pl->fb_count;
+  const nwc::Committee cm = r.lk_build ? launch_committee_of(d) : committee_of(d);
+  nwc::VerifyArgs a{q.msgs, q.msg_index, q.msg_stride, q.pks, q.sigs, q.out_words, n, q.strict, d.base_table, d.base24,
+                    d.scratch, d.fb_list, d.fb_count, settings().force_fallback_every, cm};
+  if (q.pair) {
+    a.scratch = d.scratch + (size_t)(q.pair->half ? cap / 2 : 0) * 256 * 2 * nwc::TAB_BYTES_PER_LANE;
+    a.fb_list = q.pair->fb_list;
+    a.fb_count = q.pair->fb_count;
   }
   a.force_windows = knobs().force_windows.load();
   a.stamps = d.stamps;
-  const nwc::CombArgs ca{d.uc_list, d.uc_count, d.comb_base, d.comb16, nullptr, (uint32_t)(defer ? list_base : 0)};
-  const bool half = path != VPath::Full;
-  // small batch-leaf launches outside the comb path: the keys' torsion test (one long serial
-  // lane per new key) runs on the side stream beside the verification instead of after it
-  // a small batch no cache covers (first-sight keys): one limb-sliced block per equation, the
-  // batch leaf's torsion test inside it
-  const bool cold = half && !comb && !cm.n && n <= cold_max() && cold_path() && !pair;
-  const bool tors_beside = !strict && !comb && n <= NWC_WIDE_MAX && !cold;
-  if (tors_beside) {
+  const nwc::CombArgs ca{d.uc_list, d.uc_count, d.comb_base, d.comb16, nullptr, (uint32_t)(defer ? q.list_base : 0)};
+  if (r.torsion == Torsion::Beside) {
     HIP_TRY(hipEventRecord(d.ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(d.side, d.ev_fork, 0));
-    if (int rc = launch_torsion(d, pks, out_words, n, nullptr, nullptr, cm, d.side, 1, 1)) return rc;
+    if (int rc = launch_torsion(d, q.pks, q.out_words, n, nullptr, nullptr, cm, d.side, 1, 1)) return rc;
     HIP_TRY(hipEventRecord(d.ev_join, d.side));
   }
-  if (defer && sr) {
-    // R' and the projective y test now, the sign of x(R') later in k_comb_sign over many votes
-    // (or in the first blocks of the next such launch: sp, the previous launch's votes)
-    const unsigned gy = (unsigned)std::min<uint64_t>(tiles, 60000);
-    if (sp && sp->n)
-      hipLaunchKernelGGL(nwc::k_verify_comb_y_sign, dim3(gy + sp->blocks), dim3(256), 0, s, a, ca, *sr, *sp);
-    else
-      hipLaunchKernelGGL(nwc::k_verify_comb_y, dim3(gy), dim3(256), 0, s, a, ca, *sr);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d.scratch_free, s));
-    return 0;
-  }
-  if (defer) {
-    if (n <= NWC_WIDE_MAX) {
-      HIP_TRY(hipMemsetAsync(out_words, 0, 8 * ((n + 63) / 64), s));
+  if (r.zero_fb_count) HIP_TRY(hipMemsetAsync(a.fb_count, 0, sizeof(uint32_t), s));
+  if (r.list_pass) HIP_TRY(hipMemsetAsync(d.uc_count, 0, sizeof(uint32_t), s));
+  if (r.zero_words) HIP_TRY(hipMemsetAsync(q.out_words, 0, 8 * r.zero_words, s));
+  // R' and the projective y test now, the sign of x(R') later in k_comb_sign over many votes (or
+  // in the first blocks of the next such launch: sign_pass, the previous launch's votes)
+  const unsigned gy = (unsigned)std::min<uint64_t>(tiles, 60000);
+  switch (r.kernel) {
+    case Kernel::CombYSign:
+      hipLaunchKernelGGL(nwc::k_verify_comb_y_sign, dim3(gy + q.sign_pass->blocks), dim3(256), 0, s, a, ca, *q.sign_recs,
+                         *q.sign_pass);
+      break;
+    case Kernel::CombY:
+      hipLaunchKernelGGL(nwc::k_verify_comb_y, dim3(gy), dim3(256), 0, s, a, ca, *q.sign_recs);
+      break;
+    case Kernel::CombWide:   // small batches: one block per equation, critical path = one square root
       hipLaunchKernelGGL(nwc::k_verify_comb_wide, dim3((unsigned)n), dim3(128), 0, s, a, ca);
-    } else {
+      break;
+    case Kernel::Comb:
       hipLaunchKernelGGL(nwc::k_verify_comb, dim3(gridc), dim3(256), 0, s, a, ca);
-    }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d.scratch_free, s));
-    return 0;
+      break;
+    case Kernel::Cold:
+      hipLaunchKernelGGL(nwc::k_verify_cold, dim3((unsigned)n), dim3(256), 0, s, a, (const nwc::ge_niels_pad*)d.comb16,
+                         (uint8_t*)nullptr);
+      break;
+    case Kernel::HalfCached:
+      hipLaunchKernelGGL((nwc::k_verify<true, true>), dim3(grid), dim3(256), 0, s, a, ca);
+      break;
+    case Kernel::HalfStamp:
+      hipLaunchKernelGGL((nwc::k_verify<true, false, false, true>), dim3(grid), dim3(256), 0, s, a, ca);
+      break;
+    case Kernel::Half:
+      hipLaunchKernelGGL((nwc::k_verify<true, false>), dim3(grid), dim3(256), 0, s, a, ca);
+      break;
+    case Kernel::Full:
+      hipLaunchKernelGGL((nwc::k_verify<false, false>), dim3(grid), dim3(256), 0, s, a, ca);
+      break;
+    default:
+      return set_err(NWC_ERR_ARG, "a single-kernel route among the listed launches");
   }
-  if (half) HIP_TRY(hipMemsetAsync(a.fb_count, 0, sizeof(uint32_t), s));
-  if (comb) {
-    HIP_TRY(hipMemsetAsync(d.uc_count, 0, sizeof(uint32_t), s));
-    if (sr) {
-      // sign test deferred (the chunked host path, verify_range): the words zeroed for the list
-      // passes and the later sign pass to OR into; the previous chunk's sign pass in front
-      HIP_TRY(hipMemsetAsync(out_words, 0, 8 * ((n + 63) / 64), s));
-      const unsigned gy = (unsigned)std::min<uint64_t>(tiles, 60000);
-      if (sp && sp->n)
-        hipLaunchKernelGGL(nwc::k_verify_comb_y_sign, dim3(gy + sp->blocks), dim3(256), 0, s, a, ca, *sr, *sp);
-      else
-        hipLaunchKernelGGL(nwc::k_verify_comb_y, dim3(gy), dim3(256), 0, s, a, ca, *sr);
-    } else if (n <= NWC_WIDE_MAX) {
-      // small batches: one block per equation, critical path = one square root
-      HIP_TRY(hipMemsetAsync(out_words, 0, 8 * ((n + 63) / 64), s));
-      hipLaunchKernelGGL(nwc::k_verify_comb_wide, dim3((unsigned)n), dim3(128), 0, s, a, ca);
-    } else {
-      hipLaunchKernelGGL(nwc::k_verify_comb, dim3(gridc), dim3(256), 0, s, a, ca);
-    }
-    HIP_TRY(hipGetLastError());
+  HIP_TRY(hipGetLastError());
+  if (r.list_pass) {
     // uncached keys: half-size equations in list mode (waves exit at once when the list is empty)
     nwc::VerifyArgs l = a;
     l.committee.n = 0;
     hipLaunchKernelGGL((nwc::k_verify<true, false, true>), dim3(grid), dim3(256), 0, s, l, ca);
-  } else if (cold) {
-    if (!(flags & LV_OUT_ZEROED)) HIP_TRY(hipMemsetAsync(out_words, 0, 8 * ((n + 63) / 64), s));
-    hipLaunchKernelGGL(nwc::k_verify_cold, dim3((unsigned)n), dim3(256), 0, s, a, (const nwc::ge_niels_pad*)d.comb16,
-                       (uint8_t*)nullptr);
-  } else {
-    if (half && cm.n)
-      hipLaunchKernelGGL((nwc::k_verify<true, true>), dim3(grid), dim3(256), 0, s, a, ca);
-    else if (half && (flags & LV_STAMP))
-      hipLaunchKernelGGL((nwc::k_verify<true, false, false, true>), dim3(grid), dim3(256), 0, s, a, ca);
-    else if (half)
-      hipLaunchKernelGGL((nwc::k_verify<true, false>), dim3(grid), dim3(256), 0, s, a, ca);
-    else
-      hipLaunchKernelGGL((nwc::k_verify<false, false>), dim3(grid), dim3(256), 0, s, a, ca);
+    HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipGetLastError());
-  if (half && !pair) {
+  if (r.fallback) {
     // lanes whose reduction failed are rare (|c| or d >= 2^147); a few blocks suffice
     const unsigned fgrid = grid < 16u ? grid : 16u;
     hipLaunchKernelGGL(nwc::k_verify_fallback, dim3(fgrid), dim3(256), 0, s, a);
     HIP_TRY(hipGetLastError());
   }
-  // batch leaves: keys with torsion (cached keys were checked in the comb kernels; the comb
-  // path's other equations are its uncached list)
-  if (tors_beside) {
+  if (r.torsion == Torsion::Beside) {
     HIP_TRY(hipStreamWaitEvent(s, d.ev_join, 0));
-    if (int rc = launch_torsion(d, pks, out_words, n, nullptr, nullptr, cm, s, 2, 1)) return rc;
-  } else if (!strict && !cold) {
-    if (int rc = launch_torsion(d, pks, out_words, n, comb ? d.uc_list : nullptr, comb ? d.uc_count : nullptr, cm, s))
+    if (int rc = launch_torsion(d, q.pks, q.out_words, n, nullptr, nullptr, cm, s, 2, 1)) return rc;
+  } else if (r.torsion != Torsion::None) {
+    const bool list = r.torsion == Torsion::AfterList;
+    if (int rc = launch_torsion(d, q.pks, q.out_words, n, list ? d.uc_list : nullptr, list ? d.uc_count : nullptr, cm, s))
       return rc;
   }
-  if (!pair) HIP_TRY(hipEventRecord(d.scratch_free, s));
+  if (r.scratch_order) HIP_TRY(hipEventRecord(d.scratch_free, s));
   return 0;
+}
+
+int launch_verify(DevCtx& d, const VerifyLaunch& q) {
+  if (q.n == 0) return 0;
+  if (int rc = ensure_verify_tables(d)) return rc;
+  if (int rc = release_idle_buffers(d, nullptr)) return rc;
+  const nwc::plan::DeviceView view = device_view(d);
+  const nwc::plan::Request req{q.n, q.strict != 0, q.flags, q.list_base, q.vbytes != nullptr, q.pair != nullptr,
+                               q.sign_recs != nullptr, q.sign_pass && q.sign_pass->n};
+  if (nwc::plan::splits(view, req)) {
+    // consecutive launches of at most NWC_VERIFY_MAX_LAUNCH equations (a multiple of 64: whole
+    // verdict words), so the per-launch lists stay bounded; every equation is independent, so the
+    // verdicts are those of one launch (launch keys and the torsion set are per launch anyway)
+    const uint64_t step = view.verify_max_launch;
+    for (uint64_t lo = 0; lo < q.n; lo += step) {
+      VerifyLaunch part = q;
+      if (!q.msg_index) part.msgs = q.msgs + 32 * lo * q.msg_stride;
+      if (q.msg_index) part.msg_index = q.msg_index + lo;
+      part.pks = q.pks + 32 * lo;
+      part.sigs = q.sigs + 64 * lo;
+      part.n = std::min(step, q.n - lo);
+      part.out_words = q.out_words + lo / 64;
+      part.list_base = q.list_base + lo;
+      part.pair = nullptr;
+      part.sign_recs = nullptr;
+      part.sign_pass = nullptr;
+      if (int rc = launch_verify(d, part)) return rc;
+    }
+    return 0;
+  }
+  const nwc::plan::Route r = nwc::plan::route_verify(view, req);
+  if (nwc::plan::early_error(r)) return set_err(NWC_ERR_ARG, "%s", r.error);
+  return r.scratch ? enqueue_listed(d, q, r) : enqueue_single(d, q, r);   // (enqueue_listed returns a late error)
 }
 
 // The passes LV_DEFER_LIST launches left out, once over equations [0, n) of the arrays they were
@@ -1092,9 +1012,9 @@ int finish_deferred_list(DevCtx& d, const uint8_t* msgs, const uint32_t* msg_ind
   const unsigned grid = (unsigned)(tiles < cap ? tiles : cap);
   if (int rc = ensure_scratch(d, (size_t)cap * 256 * 2 * nwc::TAB_BYTES_PER_LANE, d.fb_cap)) return rc;
   HIP_TRY(hipStreamWaitEvent(s, d.scratch_free, 0));
-  const nwc::Committee cm{d.cm_keys, d.cm_flags, d.cm_tables, d.cm_comb, d.cm_slots, d.cm_slot_mask, d.cm_n};
+  const nwc::Committee cm = committee_of(d);
   nwc::VerifyArgs a{msgs, msg_index, msg_stride, pks, sigs, out_words, n, strict, d.base_table, d.base24, d.scratch,
-                    d.fb_list, d.fb_count, force_fallback_every(), cm};
+                    d.fb_list, d.fb_count, settings().force_fallback_every, cm};
   a.force_windows = knobs().force_windows.load();
   a.stamps = d.stamps;
   const nwc::CombArgs ca{d.uc_list, d.uc_count, d.comb_base, d.comb16};
@@ -1131,39 +1051,6 @@ int launch_comb_sign(DevCtx& d, const nwc::SignRecs& sr, uint64_t v0, uint64_t n
   return 0;
 }
 
-// NWC_SIGN_DEFER=0: the comb path decides the sign in k_verify_comb everywhere (A/B of the
-// deferred sign tests of chunked launches: the message pipeline and large host calls)
-bool sign_defer() {
-  static const bool on = [] {
-    const char* e = std::getenv("NWC_SIGN_DEFER");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
-}
-// NWC_STRICT_Y=0: the message pipeline's strict equations through launch_verify on the leaf
-// stream (A/B of the list-free strict launches on the parse stream)
-bool strict_y_on() {
-  static const bool on = [] {
-    const char* e = std::getenv("NWC_STRICT_Y");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  return on;
-}
-// Whether launch_verify takes the comb path (k_verify_comb) for a plain launch of n equations.
-bool takes_comb_path(const DevCtx& d, uint64_t n, int strict) {
-  if (verify_path() != VPath::Default) return false;
-  const bool lk = !strict && !d.cm_n && d.comb16 && n >= nwc::LK_MIN_EQUATIONS && knobs().launch_keys.load();
-  return lk || (d.cm_n && d.cm_comb && (n <= NWC_WIDE_MAX || d.comb16));
-}
-// NWC_DIGEST_SCHED=0/1 forces the one-lane-per-message / scheduled digest kernel (A/B and tests).
-int digest_sched_mode() {
-  static const int mode = [] {
-    const char* e = std::getenv("NWC_DIGEST_SCHED");
-    return e ? std::atoi(e) : -1;
-  }();
-  return mode;
-}
-
 int launch_digest(const uint8_t* data, const uint64_t* offsets, const uint64_t* ends, uint64_t n, uint8_t* out32,
                   hipStream_t s) {
   if (n == 0) return 0;
@@ -1172,7 +1059,7 @@ int launch_digest(const uint8_t* data, const uint64_t* offsets, const uint64_t* 
   int cus = 0;
   HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
   // more than one wave per SIMD of one-lane-per-message work: schedule blocks instead
-  const int mode = digest_sched_mode();
+  const int mode = settings().digest_sched;   // NWC_DIGEST_SCHED=0/1 forces a kernel (A/B and tests)
   const bool sched = mode >= 0 ? mode == 1 : n > 64ull * 4 * (uint64_t)cus;
   if (sched) {
     hipLaunchKernelGGL(nwc::k_sha512_digest32_sched, dim3((unsigned)cus), dim3(256), 0, s, data, offsets, ends, n,
@@ -1266,9 +1153,305 @@ void launch_cert_index(const uint32_t* doffs, uint64_t c_lo, uint64_t c_end, uin
   hipLaunchKernelGGL(nwc::k_cert_index, dim3(grid), dim3(256), 0, s, doffs, (uint32_t)c_lo, (uint32_t)ncert, lo, hi, dmi);
 }
 
-// Host-memory verification of equations [lo, hi) on device di.  Batch mode (cert_offsets, the m + 1
-// vote offsets of the call's certificates; msgs = their m digests): equation v checks digest c with
-// offsets[c] <= v < offsets[c + 1], the index built on the device for large ranges.
+// One host-memory verification call on a device: the caller's arrays, its equations [lo, lo + n)
+// and their places in the device arena.  Batch mode (cert_offsets, the m + 1 vote offsets of the
+// call's certificates; msgs = their m digests): equation v checks digest c with
+// offsets[c] <= v < offsets[c + 1], c in [c_lo, c_end).
+struct HostCall {
+  const uint8_t* msgs;
+  uint64_t msg_stride;
+  const uint32_t* cert_offsets;
+  const uint8_t* pks;
+  const uint8_t* sigs;
+  uint64_t lo, n, words, nmsgs;
+  int strict;
+  uint64_t c_lo = 0, c_end = 0;
+  uint64_t msg_bytes = 0;
+  size_t need = 0, offs_bytes = 0;   // arena bytes up to the verdict words' end; of the offsets after them
+  uint8_t* dm = nullptr;
+  uint32_t* dmi = nullptr;     // batch: vote -> certificate index
+  uint8_t* dp = nullptr;
+  uint8_t* ds = nullptr;
+  uint64_t* dout = nullptr;    // words + the latency kernel's missing-key word
+  uint32_t* doffs = nullptr;   // batch, large ranges: k_cert_index's input
+  bool batch() const { return cert_offsets != nullptr; }
+  // the launch of equations [c0, c0 + len) of the device arrays on s
+  VerifyLaunch launch(uint64_t c0, uint64_t len, hipStream_t s) const {
+    return {.msgs = msg_stride ? dm + 32 * c0 : dm, .msg_index = batch() ? dmi + c0 : nullptr, .msg_stride = msg_stride ? 1u : 0u,
+            .pks = dp + 32 * c0, .sigs = ds + 64 * c0, .n = len, .strict = strict, .out_words = dout + c0 / 64, .stream = s};
+  }
+};
+
+// Inputs of equations [c0, c0 + len) through the pinned stages on the transfer stream; ev is
+// recorded behind them.
+int stage_chunk(DevCtx& d, const HostCall& c, uint64_t c0, uint64_t len, hipEvent_t ev) {
+  HostStager& hs = *d.stager;
+  if (c.msg_stride) HIP_TRY(hs.put(c.dm + 32 * c0, c.msgs + 32 * (c.lo + c0), 32 * len));
+  HIP_TRY(hs.put(c.dp + 32 * c0, c.pks + 32 * (c.lo + c0), 32 * len));
+  HIP_TRY(hs.put(c.ds + 64 * c0, c.sigs + 64 * (c.lo + c0), 64 * len));
+  HIP_TRY(hs.flush());
+  HIP_TRY(hipEventRecord(ev, d.xfer));
+  return 0;
+}
+
+// The verdict words to the host once the device stream is done (NWC_HOST_TIMING: the phases' times).
+int collect_words(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words, const char* kind, uint64_t nch,
+                  std::chrono::steady_clock::time_point tv0) {
+  const auto tq = std::chrono::steady_clock::now();
+  HIP_TRY(hipMemcpyAsync(out_words.data(), c.dout, 8 * c.words, hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(hipStreamSynchronize(d.stream));
+  if (settings().host_timing)
+    std::fprintf(stderr, "nwc host call%s: %llu equations in %llu chunks: copies queued after %.2f ms, done %.2f ms later\n", kind,
+                 (unsigned long long)c.n, (unsigned long long)nch, std::chrono::duration<double>(tq - tv0).count() * 1e3,
+                 std::chrono::duration<double>(std::chrono::steady_clock::now() - tq).count() * 1e3);
+  return 0;
+}
+
+// Small call (a certificate, a header): packed into pinned memory, then one H2D and one D2H -- or,
+// with every key cached or none (first sight), read in place by one kernel that stores a verdict
+// byte per equation there (zero copy).
+int verify_small(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words) {
+  using nwc::plan::SmallMode;
+  const uint64_t n = c.n, words = c.words;
+  if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
+  uint8_t* h = d.pinned;
+  const uint8_t* keys = c.pks + 32 * c.lo;
+  std::memcpy(h + (c.dm - d.arena), c.batch() ? c.msgs : c.msgs + (c.msg_stride ? 32 * c.lo : 0), c.msg_bytes);
+  if (c.batch())
+    fill_cert_index(reinterpret_cast<uint32_t*>(h + ((uint8_t*)c.dmi - d.arena)), c.cert_offsets, c.c_lo, c.c_end, c.lo, c.lo + n);
+  std::memcpy(h + (c.dp - d.arena), keys, 32 * n);
+  std::memcpy(h + (c.ds - d.arena), c.sigs + 64 * c.lo, 64 * n);
+  std::memset(h + ((uint8_t*)c.dout - d.arena), 0, 8 * (words + 1));
+  const bool cm_hit = d.cm_n && g_hcm.all_cached(keys, n);
+  const bool ak_hit = !cm_hit && d.ak_n && n <= NWC_WIDE_MAX && d.ak_host.all_found(keys, n);
+  const nwc::plan::SmallRoute sr =
+      nwc::plan::small_call_route(device_view(d), settings(), n, cm_hit, ak_hit, c.need, NWC_PINNED_STAGE_MAX);
+  int fl = sr.flags;
+  const size_t staged_bytes = (size_t)((uint8_t*)c.dout - d.arena) + 8 * (words + 1);
+  if (sr.mode != SmallMode::Staged) {
+    uint8_t* hb = h + align256(c.need);   // byte verdicts of a zero-copy launch, after the staged inputs
+    std::memset(hb, 0, n);
+    auto dev = [&](const void* p) { return p ? d.pinned_dev + ((const uint8_t*)p - d.arena) : nullptr; };
+    VerifyLaunch zc = c.launch(0, n, d.stream);
+    zc.msgs = dev(c.dm);
+    zc.msg_index = reinterpret_cast<const uint32_t*>(dev(c.dmi));
+    zc.pks = dev(c.dp);
+    zc.sigs = dev(c.ds);
+    zc.flags = fl;
+    zc.vbytes = d.pinned_dev + (hb - h);
+    if (int rc = launch_verify(d, zc)) return rc;
+    // poll the verdict bytes (bit 7 = written); a launch that never writes them (a device error)
+    // falls back to the stream wait after 200 ms, which reports the error
+    const bool spin = settings().spin_wait;   // 0 = wait for the stream (A/B)
+    if (!spin || !nwc::plan::poll_written(hb, n, std::chrono::milliseconds(200))) {
+      HIP_TRY(hipStreamSynchronize(d.stream));
+      if (spin && !nwc::plan::poll_written(hb, n, std::chrono::microseconds(0)))
+        return set_err(NWC_ERR_DEVICE, "latency kernel left verdicts unwritten");
+    }
+    bool missing = false;
+    for (uint64_t i = 0; i < n; ++i) {
+      if (hb[i] & 1) out_words[i >> 6] |= 1ull << (i & 63);
+      missing = missing || (hb[i] & 2);
+    }
+    if (!missing) return sr.mode == SmallMode::ZeroCopyCold ? auto_insert(d, keys, n) : 0;
+    // a key was missing on the device after all (cold: a reduction failed): stage the inputs
+    // and run the general path
+    std::fill(out_words.begin(), out_words.end(), 0);
+    fl &= ~(LV_ALL_CACHED | LV_AUTO);
+  }
+  HIP_TRY(hipMemcpyAsync(d.arena, h, staged_bytes, hipMemcpyHostToDevice, d.stream));
+  VerifyLaunch q = c.launch(0, n, d.stream);
+  q.flags = fl;
+  if (int rc = launch_verify(d, q)) return rc;
+  HIP_TRY(hipMemcpyAsync(h, c.dout, 8 * (words + 1), hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(hipStreamSynchronize(d.stream));
+  if ((fl & LV_ALL_CACHED) && h[8 * words] != 0) {
+    // a key was missing on the device after all: the general path decides every equation
+    if (int rc = launch_verify(d, c.launch(0, n, d.stream))) return rc;
+    HIP_TRY(hipMemcpyAsync(h, c.dout, 8 * words, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+  }
+  std::memcpy(out_words.data(), h, 8 * words);
+  if (!(fl & LV_ALL_CACHED) && n <= NWC_WIDE_MAX && settings().verify_path == VPath::Default)
+    if (int rc = auto_insert(d, keys, n)) return rc;
+  return 0;
+}
+
+// Strict calls without a committee cache: the paired pipeline.  Chunks alternate between the
+// device stream and the side stream, each launch on its own half of the table slots with its own
+// fallback count and list region (PairLaunch), so chunk k + 1's blocks take the slots chunk k's
+// drain frees instead of waiting for its last block, and the first chunk can be small
+// (NWC_HOST_PAIR_FIRST, 65,536 equations = 8 MB of inputs, then x NWC_HOST_PAIR_GROWTH = 2).
+// The fallback passes run once the streams have joined.  NWC_HOST_PAIR=0: the single-stream
+// chunks (verify_chunked, A/B).
+int verify_paired(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words) {
+  const nwc::plan::Settings& st = settings();
+  const uint64_t n = c.n;
+  if (int rc = ensure_stager(d)) return rc;
+  if (int rc = ensure_verify_tables(d)) return rc;
+  if (int rc = release_idle_buffers(d, d.pair_buf)) return rc;
+  d.stager->reset();
+  const auto tv0 = std::chrono::steady_clock::now();
+  const std::vector<uint64_t> cuts = nwc::plan::chunk_cuts(n, st.host_pair_first, st.host_pair_growth, st.host_pair_max);
+  const uint64_t nch = cuts.size() - 1;
+  if (int rc = ensure_events(d.ev_chunk, nch)) return rc;
+  // slots, lists and the per-chunk counts and list regions sized once, before any launch: inside
+  // the pipeline nothing is reallocated under a running chunk (hold_lists: no shrink either)
+  const uint64_t gcap = (uint64_t)d.cus * d.verify_blocks_per_cu * NWC_VERIFY_GRID_MULT;
+  if (int rc = ensure_scratch(d, (size_t)gcap * 256 * 2 * nwc::TAB_BYTES_PER_LANE, nwc::plan::longest_chunk(cuts))) return rc;
+  const size_t counts_bytes = align256(4 * nch), pair_need = counts_bytes + 4 * n;
+  if (pair_need > d.pair_cap)
+    if (int rc = regrow(d, d.pair_buf, d.pair_cap, pair_need, nullptr, 0)) return rc;
+  uint32_t* const counts = reinterpret_cast<uint32_t*>(d.pair_buf);
+  uint32_t* const lists = reinterpret_cast<uint32_t*>(d.pair_buf + counts_bytes);
+  struct Hold {
+    DevCtx& d;
+    ~Hold() {
+      d.hold_lists = false;
+      d.busy_buf = nullptr;
+    }
+  } hold{d};
+  d.hold_lists = true;
+  d.busy_buf = d.pair_buf;
+  // the previous call's kernels may still read the arena and the slots: the copies wait for the
+  // device stream, both compute streams for scratch_free
+  HIP_TRY(hipEventRecord(d.ev_fork, d.stream));
+  HIP_TRY(hipStreamWaitEvent(d.xfer, d.ev_fork, 0));
+  HIP_TRY(hipStreamWaitEvent(d.side, d.ev_fork, 0));
+  HIP_TRY(hipStreamWaitEvent(d.stream, d.scratch_free, 0));
+  HIP_TRY(hipStreamWaitEvent(d.side, d.scratch_free, 0));
+  if (!c.msg_stride) HIP_TRY(d.stager->put(c.dm, c.msgs, 32));
+  for (uint64_t k = 0; k < nch; ++k) {
+    const uint64_t c0 = cuts[k], len = cuts[k + 1] - cuts[k];
+    if (int rc = stage_chunk(d, c, c0, len, d.ev_chunk[k])) return rc;
+    const hipStream_t sk = (k & 1) ? d.side : d.stream;
+    HIP_TRY(hipStreamWaitEvent(sk, d.ev_chunk[k], 0));
+    const PairLaunch pl{(int)(k & 1), lists + c0, counts + k};
+    VerifyLaunch q = c.launch(c0, len, sk);
+    q.pair = &pl;
+    if (int rc = launch_verify(d, q)) return rc;
+  }
+  HIP_TRY(hipEventRecord(d.ev_join, d.side));
+  HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_join, 0));
+  // every chunk's failed reductions (rare: waves exit at once on an empty list)
+  for (uint64_t k = 0; k < nch; ++k) {
+    const uint64_t c0 = cuts[k], len = cuts[k + 1] - cuts[k];
+    const nwc::VerifyArgs a{c.msg_stride ? c.dm + 32 * c0 : c.dm, nullptr, c.msg_stride ? 1u : 0u, c.dp + 32 * c0, c.ds + 64 * c0,
+                            c.dout + c0 / 64, len, c.strict, d.base_table, d.base24, d.scratch, lists + c0, counts + k,
+                            0u, nwc::Committee{}};
+    hipLaunchKernelGGL(nwc::k_verify_fallback, dim3(16), dim3(256), 0, d.stream, a);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipEventRecord(d.scratch_free, d.stream));
+  return collect_words(d, c, out_words, " (paired)", nch, tv0);
+}
+
+// Pipelined: inputs of chunk k on the transfer stream, its verification on the device stream
+// after the chunk's event; every chunk has its own region of the arena (no reuse hazards).
+// Chunk k + 1 is up to NWC_HOST_CHUNK_GROWTH x chunk k: its 128 B per equation cross PCIe
+// (~50 GB/s) while chunk k verifies (~100 M/s), so it arrives in time while growing up to ~3.7x;
+// fewer, larger launches leave fewer kernel tails (the first chunk is one round of resident
+// lanes).  Chunks stop growing at NWC_HOST_CHUNK_MAX equations: when the kernels keep pace with
+// the copies (the comb kernel: ~640 M votes/s against ~600 M votes/s of inputs through the stages)
+// a huge last chunk would start only once all its inputs are in and run alone at the end.
+int verify_chunked(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words) {
+  const nwc::plan::Settings& st = settings();
+  if (int rc = ensure_stager(d)) return rc;
+  HostStager* const hs = d.stager.get();
+  hs->reset();
+  const auto tv0 = std::chrono::steady_clock::now();
+  const std::vector<uint64_t> cuts = nwc::plan::chunk_cuts(c.n, st.host_chunk, st.host_chunk_growth, st.host_chunk_max);
+  const uint64_t nch = cuts.size() - 1;
+  if (int rc = ensure_events(d.ev_chunk, nch)) return rc;
+  // Chunks on the comb path (launch keys or the committee cache) defer their sign tests: a
+  // lane gets ~8 votes of a 1M-vote chunk, and its one inversion would be ~9 % of each vote's
+  // work (k_verify_comb_y; the sign pass of chunk k runs in the first blocks of chunk k + 1's
+  // launch, the last one alone; SignRecs of two chunks alternate in sign_buf)
+  const uint64_t maxlen = nwc::plan::longest_chunk(cuts);
+  const bool ysplit = !c.strict && st.sign_defer;
+  nwc::SignRecs reg[2] = {};
+  if (ysplit) {
+    if (int rc = release_idle_buffers(d, d.sign_buf)) return rc;
+    const size_t need_s = 2 * (3 * align256(32 * maxlen) + align256(4 * maxlen));
+    if (need_s > d.sign_cap)
+      if (int rc = regrow(d, d.sign_buf, d.sign_cap, need_s, nullptr, 0)) return rc;
+    Carve cs(d.sign_buf);
+    for (auto& r : reg) {
+      r.x = cs.take<uint32_t>(32 * maxlen);
+      r.z = cs.take<uint32_t>(32 * maxlen);
+      r.p = cs.take<uint32_t>(32 * maxlen);
+      r.meta = cs.take<uint32_t>(4 * maxlen);
+    }
+  }
+  uint64_t owed_c0 = 0, owed_len = 0;   // the chunk whose sign tests are still to run
+  int owed_reg = 0;
+  struct Busy {
+    DevCtx& d;
+    ~Busy() { d.busy_buf = nullptr; }
+  } busy{d};
+  d.busy_buf = d.sign_buf;
+  // the previous call's kernels may still read the arena: the transfers wait for the stream
+  HIP_TRY(hipEventRecord(d.ev_fork, d.stream));
+  HIP_TRY(hipStreamWaitEvent(d.xfer, d.ev_fork, 0));
+  if (c.batch()) {
+    // digests and offsets first; the vote index is built on the device behind them, so chunk 0's
+    // event (recorded later on the same stream) covers it
+    HIP_TRY(hs->put(c.dm, c.msgs, c.msg_bytes));
+    HIP_TRY(hs->put(reinterpret_cast<uint8_t*>(c.doffs), reinterpret_cast<const uint8_t*>(c.cert_offsets + c.c_lo), c.offs_bytes));
+    HIP_TRY(hs->flush());
+    launch_cert_index(c.doffs, c.c_lo, c.c_end, c.lo, c.lo + c.n, c.dmi, d.xfer);
+    HIP_TRY(hipGetLastError());
+  } else if (!c.msg_stride) {
+    HIP_TRY(hs->put(c.dm, c.msgs, 32));
+  }
+  for (uint64_t k = 0; k < nch; ++k) {
+    const uint64_t c0 = cuts[k], len = cuts[k + 1] - cuts[k];
+    if (int rc = stage_chunk(d, c, c0, len, d.ev_chunk[k])) return rc;
+    HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_chunk[k], 0));
+    const nwc::SignPass sp{sign_recs_at(reg[owed_reg], -(int64_t)owed_c0), owed_c0, owed_len, c.dout,
+                           comb_sign_blocks(d, owed_len)};
+    const bool y = ysplit && takes_comb_path(d, len, c.strict);
+    if (!y && owed_len) {
+      if (int rc = launch_comb_sign(d, sp.rec, owed_c0, owed_len, c.dout, d.stream)) return rc;
+      owed_len = 0;
+    }
+    const int r = (int)(k & 1);
+    VerifyLaunch q = c.launch(c0, len, d.stream);
+    q.sign_recs = y ? &reg[r] : nullptr;
+    q.sign_pass = y && owed_len ? &sp : nullptr;
+    if (int rc = launch_verify(d, q)) return rc;
+    if (y) {
+      owed_c0 = c0;
+      owed_len = len;
+      owed_reg = r;
+    }
+  }
+  if (owed_len)
+    if (int rc = launch_comb_sign(d, sign_recs_at(reg[owed_reg], -(int64_t)owed_c0), owed_c0, owed_len, c.dout, d.stream))
+      return rc;
+  return collect_words(d, c, out_words, "", nch, tv0);
+}
+
+// One copy of everything, one launch, one copy back.
+int verify_direct(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words) {
+  if (c.batch()) {
+    HIP_TRY(hipMemcpyAsync(c.dm, c.msgs, c.msg_bytes, hipMemcpyHostToDevice, d.stream));
+    HIP_TRY(hipMemcpyAsync(c.doffs, c.cert_offsets + c.c_lo, c.offs_bytes, hipMemcpyHostToDevice, d.stream));
+    launch_cert_index(c.doffs, c.c_lo, c.c_end, c.lo, c.lo + c.n, c.dmi, d.stream);
+    HIP_TRY(hipGetLastError());
+  } else {
+    HIP_TRY(hipMemcpyAsync(c.dm, c.msgs + (c.msg_stride ? 32 * c.lo : 0), c.msg_bytes, hipMemcpyHostToDevice, d.stream));
+  }
+  HIP_TRY(hipMemcpyAsync(c.dp, c.pks + 32 * c.lo, 32 * c.n, hipMemcpyHostToDevice, d.stream));
+  HIP_TRY(hipMemcpyAsync(c.ds, c.sigs + 64 * c.lo, 64 * c.n, hipMemcpyHostToDevice, d.stream));
+  if (int rc = launch_verify(d, c.launch(0, c.n, d.stream))) return rc;
+  HIP_TRY(hipMemcpyAsync(out_words.data(), c.dout, 8 * c.words, hipMemcpyDeviceToHost, d.stream));
+  HIP_TRY(hipStreamSynchronize(d.stream));
+  return 0;
+}
+
+// Host-memory verification of equations [lo, hi) on device di: the arena carved for them, then the
+// pipeline their size and kind call for.
 int verify_range(int di, const uint8_t* msgs, uint64_t msg_stride, const uint32_t* cert_offsets,
                  const uint8_t* pks, const uint8_t* sigs, uint64_t lo, uint64_t hi, int strict,
                  std::vector<uint64_t>& out_words, uint64_t nmsgs) {
@@ -1279,364 +1462,27 @@ int verify_range(int di, const uint8_t* msgs, uint64_t msg_stride, const uint32_
   const uint64_t words = (n + 63) / 64;
   out_words.assign(words, 0);
   if (n == 0) return 0;
-  const bool batch = cert_offsets != nullptr;
-  uint64_t c_lo = 0, c_end = 0;
-  if (batch) cert_span(cert_offsets, nmsgs, lo, hi, c_lo, c_end);
-  const uint64_t msg_bytes = batch ? 32 * nmsgs : (msg_stride ? 32 * n : 32);
-  const size_t need = align256(msg_bytes) + align256(batch ? 4 * n : 0) + align256(32 * n) + align256(64 * n) +
-                      align256(8 * (words + 1));
-  const size_t offs_bytes = batch ? 4 * (c_end - c_lo + 1) : 0;
-  if (int rc = d.ensure_arena(need + align256(offs_bytes))) return rc;
-  Carve c(d.arena);
-  uint8_t* dm = c.take<uint8_t>(msg_bytes);
-  uint32_t* dmi = batch ? c.take<uint32_t>(4 * n) : nullptr;
-  uint8_t* dp = c.take<uint8_t>(32 * n);
-  uint8_t* ds = c.take<uint8_t>(64 * n);
-  uint64_t* dout = c.take<uint64_t>(8 * (words + 1));   // + the latency kernel's missing-key word
-  uint32_t* doffs = batch ? c.take<uint32_t>(offs_bytes) : nullptr;   // large ranges: k_cert_index's input
-  if (need <= NWC_PINNED_STAGE_MAX) {
-    // small call (a certificate, a header): pack into pinned memory, one H2D, one D2H
-    if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
-    uint8_t* h = d.pinned;
-    std::memcpy(h + (dm - d.arena), batch ? msgs : msgs + (msg_stride ? 32 * lo : 0), msg_bytes);
-    if (batch) fill_cert_index(reinterpret_cast<uint32_t*>(h + ((uint8_t*)dmi - d.arena)), cert_offsets, c_lo, c_end, lo, hi);
-    std::memcpy(h + (dp - d.arena), pks + 32 * lo, 32 * n);
-    std::memcpy(h + (ds - d.arena), sigs + 64 * lo, 64 * n);
-    std::memset(h + ((uint8_t*)dout - d.arena), 0, 8 * (words + 1));
-    int fl = LV_OUT_ZEROED;
-    if (d.cm_n && g_hcm.all_cached(pks + 32 * lo, n)) fl |= LV_ALL_CACHED;
-    else if (d.ak_n && n <= NWC_WIDE_MAX && d.ak_host.all_found(pks + 32 * lo, n)) fl |= LV_ALL_CACHED | LV_AUTO;
-    const size_t vb_off = align256(need);   // byte verdicts of a zero-copy launch, after the staged inputs
-    static const bool zero_copy = [] {
-      const char* e = std::getenv("NWC_ZERO_COPY");
-      return !(e && std::strcmp(e, "0") == 0);
-    }();
-    const bool zc_ok = zero_copy && n <= NWC_WIDE_MAX && vb_off + n <= NWC_PINNED_STAGE_MAX &&
-                       verify_path() == VPath::Default;
-    const bool zc_cached = zc_ok && (fl & LV_ALL_CACHED) && (fl & LV_AUTO ? d.ak_comb != nullptr : d.cm_comb != nullptr);
-    const bool zc_cold = zc_ok && !(fl & LV_ALL_CACHED) && !d.cm_n && cold_path();
-    if (zc_cached || zc_cold) {
-      // every key cached: the latency kernel reads the staged inputs in place from pinned host
-      // memory and stores one verdict byte per equation there -- no DMA copy either way; no key
-      // cached (first sight): the cold kernel, the same way
-      uint8_t* hb = h + vb_off;
-      std::memset(hb, 0, n);
-      auto dev = [&](const void* p) { return p ? d.pinned_dev + ((const uint8_t*)p - d.arena) : nullptr; };
-      if (int rc = launch_verify(d, dev(dm), reinterpret_cast<const uint32_t*>(dev(dmi)), msg_stride ? 1 : 0, dev(dp),
-                                 dev(ds), n, strict, dout, d.stream, fl, d.pinned_dev + (hb - h)))
-        return rc;
-      static const bool spin = [] {
-        const char* e = std::getenv("NWC_SPIN_WAIT");   // 0 = wait for the stream (A/B)
-        return !(e && std::strcmp(e, "0") == 0);
-      }();
-      if (spin) {
-        // poll the verdict bytes (bit 7 = written); a launch that never writes them (a device
-        // error) falls back to the stream wait after 200 ms, which reports the error
-        const volatile uint8_t* vb = hb;
-        const auto t0 = std::chrono::steady_clock::now();
-        uint64_t done = 0;
-        for (;;) {
-          while (done < n && (vb[done] & 0x80u)) ++done;
-          if (done == n) break;
-          if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-            HIP_TRY(hipStreamSynchronize(d.stream));
-            for (done = 0; done < n && (vb[done] & 0x80u); ++done) {}
-            if (done != n) return set_err(NWC_ERR_DEVICE, "latency kernel left verdicts unwritten");
-            break;
-          }
-          __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-      } else {
-        HIP_TRY(hipStreamSynchronize(d.stream));
-      }
-      bool missing = false;
-      for (uint64_t i = 0; i < n; ++i) {
-        if (hb[i] & 1) out_words[i >> 6] |= 1ull << (i & 63);
-        missing = missing || (hb[i] & 2);
-      }
-      if (!missing) return zc_cold ? auto_insert(d, pks + 32 * lo, n) : 0;
-      // a key was missing on the device after all (cold: a reduction failed): stage the inputs
-      // and run the general path
-      std::fill(out_words.begin(), out_words.end(), 0);
-      fl &= ~(LV_ALL_CACHED | LV_AUTO);
-      HIP_TRY(hipMemcpyAsync(d.arena, h, (size_t)((uint8_t*)dout - d.arena) + 8 * (words + 1), hipMemcpyHostToDevice,
-                             d.stream));
-    } else {
-      HIP_TRY(hipMemcpyAsync(d.arena, h, (size_t)((uint8_t*)dout - d.arena) + 8 * (words + 1), hipMemcpyHostToDevice,
-                             d.stream));
-    }
-    if (int rc = launch_verify(d, dm, dmi, msg_stride ? 1 : 0, dp, ds, n, strict, dout, d.stream, fl)) return rc;
-    HIP_TRY(hipMemcpyAsync(h, dout, 8 * (words + 1), hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    if ((fl & LV_ALL_CACHED) && h[8 * words] != 0) {
-      // a key was missing on the device after all: the general path decides every equation
-      if (int rc = launch_verify(d, dm, dmi, msg_stride ? 1 : 0, dp, ds, n, strict, dout, d.stream)) return rc;
-      HIP_TRY(hipMemcpyAsync(h, dout, 8 * words, hipMemcpyDeviceToHost, d.stream));
-      HIP_TRY(hipStreamSynchronize(d.stream));
-    }
-    std::memcpy(out_words.data(), h, 8 * words);
-    if (!(fl & LV_ALL_CACHED) && n <= NWC_WIDE_MAX && verify_path() == VPath::Default)
-      if (int rc = auto_insert(d, pks + 32 * lo, n)) return rc;
-    return 0;
-  }
-  // Strict calls without a committee cache: the paired pipeline.  Chunks alternate between the
-  // device stream and the side stream, each launch on its own half of the table slots with its own
-  // fallback count and list region (PairLaunch), so chunk k + 1's blocks take the slots chunk k's
-  // drain frees instead of waiting for its last block, and the first chunk can be small
-  // (NWC_HOST_PAIR_FIRST, 65,536 equations = 8 MB of inputs, then x NWC_HOST_PAIR_GROWTH = 2).
-  // The fallback passes run once the streams have joined.  NWC_HOST_PAIR=0: the single-stream
-  // chunks below (A/B).
-  static const bool pair_on = [] {
-    const char* e = std::getenv("NWC_HOST_PAIR");
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
-  static const uint64_t pair_first = [] {
-    const char* e = std::getenv("NWC_HOST_PAIR_FIRST");
-    return std::max<uint64_t>(64, (e ? std::strtoull(e, nullptr, 10) : 65536ull) / 64 * 64);
-  }();
-  static const uint64_t pair_growth = [] {
-    const char* e = std::getenv("NWC_HOST_PAIR_GROWTH");
-    return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : 2ull;
-  }();
-  static const uint64_t pair_max = [] {
-    const char* e = std::getenv("NWC_HOST_PAIR_MAX");
-    return std::max<uint64_t>(64, (e ? std::strtoull(e, nullptr, 10) : 1ull << 20) / 64 * 64);
-  }();
-  if (pair_on && strict && !batch && verify_path() == VPath::Default && !d.cm_n && n >= 2 * pair_first &&
-      n <= verify_max_launch()) {
-    if (int rc = ensure_stager(d)) return rc;
-    if (int rc = ensure_verify_tables(d)) return rc;
-    if (int rc = release_idle_buffers(d, d.pair_buf)) return rc;
-    HostStager* const hs = d.stager.get();
-    hs->reset();
-    const auto tv0 = std::chrono::steady_clock::now();
-    std::vector<uint64_t> cuts{0};
-    uint64_t maxlen = 0;
-    for (uint64_t len = pair_first; cuts.back() < n; len = std::min(len * pair_growth, std::max(pair_first, pair_max))) {
-      uint64_t next = std::min<uint64_t>(n, cuts.back() + len);
-      if (n - next < pair_first / 2) next = n;   // no sliver of a last chunk
-      maxlen = std::max(maxlen, next - cuts.back());
-      cuts.push_back(next);
-    }
-    const uint64_t nch = cuts.size() - 1;
-    while (d.ev_chunk.size() < nch) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      d.ev_chunk.push_back(e);
-    }
-    // slots, lists and the per-chunk counts and list regions sized once, before any launch: inside
-    // the pipeline nothing is reallocated under a running chunk (hold_lists: no shrink either)
-    const uint64_t gcap = (uint64_t)d.cus * d.verify_blocks_per_cu * NWC_VERIFY_GRID_MULT;
-    if (int rc = ensure_scratch(d, (size_t)gcap * 256 * 2 * nwc::TAB_BYTES_PER_LANE, maxlen)) return rc;
-    const size_t counts_bytes = align256(4 * nch), pair_need = counts_bytes + 4 * n;
-    if (pair_need > d.pair_cap) {
-      HIP_TRY(hipEventSynchronize(d.scratch_free));
-      if (d.pair_buf) HIP_TRY(hipFree(d.pair_buf));
-      d.pair_buf = nullptr;
-      d.pair_cap = 0;
-      HIP_TRY(hipMalloc(&d.pair_buf, pair_need));
-      d.pair_cap = pair_need;
-    }
-    uint32_t* const counts = reinterpret_cast<uint32_t*>(d.pair_buf);
-    uint32_t* const lists = reinterpret_cast<uint32_t*>(d.pair_buf + counts_bytes);
-    struct Hold {
-      DevCtx& d;
-      ~Hold() {
-        d.hold_lists = false;
-        d.busy_buf = nullptr;
-      }
-    } hold{d};
-    d.hold_lists = true;
-    d.busy_buf = d.pair_buf;
-    // the previous call's kernels may still read the arena and the slots: the copies wait for the
-    // device stream, both compute streams for scratch_free
-    HIP_TRY(hipEventRecord(d.ev_fork, d.stream));
-    HIP_TRY(hipStreamWaitEvent(d.xfer, d.ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(d.side, d.ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(d.stream, d.scratch_free, 0));
-    HIP_TRY(hipStreamWaitEvent(d.side, d.scratch_free, 0));
-    auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-      return hs->put(static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src), bytes);
-    };
-    if (!msg_stride) HIP_TRY(h2d(dm, msgs, 32));
-    for (uint64_t k = 0; k < nch; ++k) {
-      const uint64_t c0 = cuts[k], len = cuts[k + 1] - cuts[k];
-      if (msg_stride) HIP_TRY(h2d(dm + 32 * c0, msgs + 32 * (lo + c0), 32 * len));
-      HIP_TRY(h2d(dp + 32 * c0, pks + 32 * (lo + c0), 32 * len));
-      HIP_TRY(h2d(ds + 64 * c0, sigs + 64 * (lo + c0), 64 * len));
-      HIP_TRY(hs->flush());
-      HIP_TRY(hipEventRecord(d.ev_chunk[k], d.xfer));
-      const hipStream_t sk = (k & 1) ? d.side : d.stream;
-      HIP_TRY(hipStreamWaitEvent(sk, d.ev_chunk[k], 0));
-      const PairLaunch pl{(int)(k & 1), lists + c0, counts + k};
-      if (int rc = launch_verify(d, msg_stride ? dm + 32 * c0 : dm, nullptr, msg_stride ? 1 : 0, dp + 32 * c0,
-                                 ds + 64 * c0, len, strict, dout + c0 / 64, sk, 0, nullptr, 0, &pl))
-        return rc;
-    }
-    HIP_TRY(hipEventRecord(d.ev_join, d.side));
-    HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_join, 0));
-    // every chunk's failed reductions (rare: waves exit at once on an empty list)
-    for (uint64_t k = 0; k < nch; ++k) {
-      const uint64_t c0 = cuts[k], len = cuts[k + 1] - cuts[k];
-      const nwc::VerifyArgs a{msg_stride ? dm + 32 * c0 : dm, nullptr, msg_stride ? 1u : 0u, dp + 32 * c0, ds + 64 * c0,
-                              dout + c0 / 64, len, strict, d.base_table, d.base24, d.scratch, lists + c0, counts + k,
-                              0u, nwc::Committee{}};
-      hipLaunchKernelGGL(nwc::k_verify_fallback, dim3(16), dim3(256), 0, d.stream, a);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipEventRecord(d.scratch_free, d.stream));
-    const auto tq = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(out_words.data(), dout, 8 * words, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    if (host_timing())
-      std::fprintf(stderr, "nwc host call (paired): %llu equations in %llu chunks: copies queued after %.2f ms, done %.2f ms later\n",
-                   (unsigned long long)n, (unsigned long long)nch, std::chrono::duration<double>(tq - tv0).count() * 1e3,
-                   std::chrono::duration<double>(std::chrono::steady_clock::now() - tq).count() * 1e3);
-    return 0;
-  }
-  static const uint64_t chunk = [] {
-    const char* e = std::getenv("NWC_HOST_CHUNK");   // 0 = no pipelining (A/B)
-    return e ? (uint64_t)std::strtoull(e, nullptr, 10) / 64 * 64 : (uint64_t)NWC_HOST_CHUNK;
-  }();
-  static const uint64_t growth = [] {
-    const char* e = std::getenv("NWC_HOST_CHUNK_GROWTH");   // 1 = equal chunks (A/B)
-    return e ? std::max<uint64_t>(1, std::strtoull(e, nullptr, 10)) : (uint64_t)NWC_HOST_CHUNK_GROWTH;
-  }();
-  if (chunk && n >= 2 * chunk) {
-    // pipelined: inputs of chunk k on the transfer stream, its verification on the device stream
-    // after the chunk's event; every chunk has its own region of the arena (no reuse hazards).
-    // Chunk k + 1 is up to `growth` x chunk k: its 128 B per equation cross PCIe (~50 GB/s) while
-    // chunk k verifies (~100 M/s), so it arrives in time while growing up to ~3.7x; fewer, larger
-    // launches leave fewer kernel tails (the first chunk is one round of resident lanes).
-    if (int rc = ensure_stager(d)) return rc;
-    // copies of one chunk's inputs: through the pinned stages
-    HostStager* const hs = d.stager.get();
-    hs->reset();
-    const auto tv0 = std::chrono::steady_clock::now();
-    auto h2d = [&](void* dst, const void* src, size_t bytes) -> hipError_t {
-      return hs->put(static_cast<uint8_t*>(dst), static_cast<const uint8_t*>(src), bytes);
-    };
-    std::vector<uint64_t> cuts{0};
-    // chunks stop growing at NWC_HOST_CHUNK_MAX equations: when the kernels keep pace with the
-    // copies (the comb kernel: ~640 M votes/s against ~600 M votes/s of inputs through the stages)
-    // a huge last chunk would start only once all its inputs are in and run alone at the end
-    static const uint64_t chunk_max = [] {
-      const char* e = std::getenv("NWC_HOST_CHUNK_MAX");   // A/B
-      return e ? std::max<uint64_t>(64, std::strtoull(e, nullptr, 10)) : (uint64_t)NWC_HOST_CHUNK_MAX;
-    }();
-    for (uint64_t len = chunk; cuts.back() < n; len = std::min(len * growth, std::max(chunk, chunk_max))) {
-      uint64_t next = std::min<uint64_t>(n, cuts.back() + len);
-      if (n - next < chunk / 2) next = n;   // no sliver of a last chunk
-      cuts.push_back(next);
-    }
-    const uint64_t nch = cuts.size() - 1;
-    while (d.ev_chunk.size() < nch) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      d.ev_chunk.push_back(e);
-    }
-    // Chunks on the comb path (launch keys or the committee cache) defer their sign tests: a
-    // lane gets ~8 votes of a 1M-vote chunk, and its one inversion would be ~9 % of each vote's
-    // work (k_verify_comb_y; the sign pass of chunk k runs in the first blocks of chunk k + 1's
-    // launch, the last one alone; SignRecs of two chunks alternate in sign_buf)
-    uint64_t maxlen = 0;
-    for (uint64_t k = 0; k < nch; ++k) maxlen = std::max(maxlen, cuts[k + 1] - cuts[k]);
-    const bool ysplit = !strict && sign_defer();
-    nwc::SignRecs reg[2] = {};
-    if (ysplit) {
-      if (int rc = release_idle_buffers(d, d.sign_buf)) return rc;
-      const size_t per = align256(32 * maxlen);
-      const size_t need_s = 2 * (3 * per + align256(4 * maxlen));
-      if (need_s > d.sign_cap) {
-        HIP_TRY(hipEventSynchronize(d.scratch_free));
-        if (d.sign_buf) HIP_TRY(hipFree(d.sign_buf));
-        d.sign_buf = nullptr;
-        d.sign_cap = 0;
-        HIP_TRY(hipMalloc(&d.sign_buf, need_s));
-        d.sign_cap = need_s;
-      }
-      Carve cs(d.sign_buf);
-      for (auto& r : reg) {
-        r.x = cs.take<uint32_t>(32 * maxlen);
-        r.z = cs.take<uint32_t>(32 * maxlen);
-        r.p = cs.take<uint32_t>(32 * maxlen);
-        r.meta = cs.take<uint32_t>(4 * maxlen);
-      }
-    }
-    uint64_t owed_c0 = 0, owed_len = 0;   // the chunk whose sign tests are still to run
-    int owed_reg = 0;
-    struct Busy {
-      DevCtx& d;
-      ~Busy() { d.busy_buf = nullptr; }
-    } busy{d};
-    d.busy_buf = d.sign_buf;
-    // the previous call's kernels may still read the arena: the transfers wait for the stream
-    HIP_TRY(hipEventRecord(d.ev_fork, d.stream));
-    HIP_TRY(hipStreamWaitEvent(d.xfer, d.ev_fork, 0));
-    if (batch) {
-      // digests and offsets first; the vote index is built on the device behind them, so chunk 0's
-      // event (recorded later on the same stream) covers it
-      HIP_TRY(h2d(dm, msgs, msg_bytes));
-      HIP_TRY(h2d(doffs, cert_offsets + c_lo, offs_bytes));
-      HIP_TRY(hs->flush());
-      launch_cert_index(doffs, c_lo, c_end, lo, hi, dmi, d.xfer);
-      HIP_TRY(hipGetLastError());
-    } else if (!msg_stride) {
-      HIP_TRY(h2d(dm, msgs, 32));
-    }
-    for (uint64_t k = 0; k < nch; ++k) {
-      const uint64_t c0 = cuts[k], len = cuts[k + 1] - cuts[k];
-      if (msg_stride) HIP_TRY(h2d(dm + 32 * c0, msgs + 32 * (lo + c0), 32 * len));
-      HIP_TRY(h2d(dp + 32 * c0, pks + 32 * (lo + c0), 32 * len));
-      HIP_TRY(h2d(ds + 64 * c0, sigs + 64 * (lo + c0), 64 * len));
-      HIP_TRY(hs->flush());
-      HIP_TRY(hipEventRecord(d.ev_chunk[k], d.xfer));
-      HIP_TRY(hipStreamWaitEvent(d.stream, d.ev_chunk[k], 0));
-      const nwc::SignPass sp{sign_recs_at(reg[owed_reg], -(int64_t)owed_c0), owed_c0, owed_len, dout,
-                             comb_sign_blocks(d, owed_len)};
-      const bool y = ysplit && takes_comb_path(d, len, strict);
-      if (!y && owed_len) {
-        if (int rc = launch_comb_sign(d, sp.rec, owed_c0, owed_len, dout, d.stream)) return rc;
-        owed_len = 0;
-      }
-      const int r = (int)(k & 1);
-      if (int rc = launch_verify(d, msg_stride ? dm + 32 * c0 : dm, batch ? dmi + c0 : nullptr, msg_stride ? 1 : 0,
-                                 dp + 32 * c0, ds + 64 * c0, len, strict, dout + c0 / 64, d.stream, 0, nullptr, 0,
-                                 nullptr, y ? &reg[r] : nullptr, y && owed_len ? &sp : nullptr))
-        return rc;
-      if (y) {
-        owed_c0 = c0;
-        owed_len = len;
-        owed_reg = r;
-      }
-    }
-    if (owed_len)
-      if (int rc = launch_comb_sign(d, sign_recs_at(reg[owed_reg], -(int64_t)owed_c0), owed_c0, owed_len, dout, d.stream))
-        return rc;
-    const auto tq = std::chrono::steady_clock::now();
-    HIP_TRY(hipMemcpyAsync(out_words.data(), dout, 8 * words, hipMemcpyDeviceToHost, d.stream));
-    HIP_TRY(hipStreamSynchronize(d.stream));
-    if (host_timing())
-      std::fprintf(stderr, "nwc host call: %llu equations in %llu chunks: copies queued after %.2f ms, done %.2f ms later\n",
-                   (unsigned long long)n, (unsigned long long)nch, std::chrono::duration<double>(tq - tv0).count() * 1e3,
-                   std::chrono::duration<double>(std::chrono::steady_clock::now() - tq).count() * 1e3);
-    return 0;
-  }
-  if (batch) {
-    HIP_TRY(hipMemcpyAsync(dm, msgs, msg_bytes, hipMemcpyHostToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(doffs, cert_offsets + c_lo, offs_bytes, hipMemcpyHostToDevice, d.stream));
-    launch_cert_index(doffs, c_lo, c_end, lo, hi, dmi, d.stream);
-    HIP_TRY(hipGetLastError());
-  } else {
-    HIP_TRY(hipMemcpyAsync(dm, msgs + (msg_stride ? 32 * lo : 0), msg_bytes, hipMemcpyHostToDevice, d.stream));
-  }
-  HIP_TRY(hipMemcpyAsync(dp, pks + 32 * lo, 32 * n, hipMemcpyHostToDevice, d.stream));
-  HIP_TRY(hipMemcpyAsync(ds, sigs + 64 * lo, 64 * n, hipMemcpyHostToDevice, d.stream));
-  if (int rc = launch_verify(d, dm, dmi, msg_stride ? 1 : 0, dp, ds, n, strict, dout, d.stream)) return rc;
-  HIP_TRY(hipMemcpyAsync(out_words.data(), dout, 8 * words, hipMemcpyDeviceToHost, d.stream));
-  HIP_TRY(hipStreamSynchronize(d.stream));
-  return 0;
+  HostCall c{msgs, msg_stride, cert_offsets, pks, sigs, lo, n, words, nmsgs, strict};
+  const bool batch = c.batch();
+  if (batch) cert_span(cert_offsets, nmsgs, lo, hi, c.c_lo, c.c_end);
+  c.msg_bytes = batch ? 32 * nmsgs : (msg_stride ? 32 * n : 32);
+  c.need = align256(c.msg_bytes) + align256(batch ? 4 * n : 0) + align256(32 * n) + align256(64 * n) + align256(8 * (words + 1));
+  c.offs_bytes = batch ? 4 * (c.c_end - c.c_lo + 1) : 0;
+  if (int rc = d.ensure_arena(c.need + align256(c.offs_bytes))) return rc;
+  Carve cv(d.arena);
+  c.dm = cv.take<uint8_t>(c.msg_bytes);
+  c.dmi = batch ? cv.take<uint32_t>(4 * n) : nullptr;
+  c.dp = cv.take<uint8_t>(32 * n);
+  c.ds = cv.take<uint8_t>(64 * n);
+  c.dout = cv.take<uint64_t>(8 * (words + 1));
+  c.doffs = batch ? cv.take<uint32_t>(c.offs_bytes) : nullptr;
+  const nwc::plan::Settings& st = settings();
+  if (c.need <= NWC_PINNED_STAGE_MAX) return verify_small(d, c, out_words);
+  if (st.host_pair && strict && !batch && st.verify_path == VPath::Default && !d.cm_n && n >= 2 * st.host_pair_first &&
+      n <= st.verify_max_launch)
+    return verify_paired(d, c, out_words);
+  if (st.host_chunk && n >= 2 * st.host_chunk) return verify_chunked(d, c, out_words);
+  return verify_direct(d, c, out_words);
 }
 
 // A per-launch device buffer of the batch entries (MSM, Straus, resolve), grown on demand and
@@ -1645,16 +1491,9 @@ int verify_range(int di, const uint8_t* msgs, uint64_t msg_stride, const uint32_
 // these buffers records scratch_free after its last kernel, so waiting for it (and for s) drains
 // their users on any stream before the buffer is replaced.
 int ensure_buf(DevCtx& d, uint8_t*& p, size_t& cap, size_t need, hipStream_t s) {
-  const bool shrink = cap > verify_keep_bytes() && need < cap / 4;
+  const bool shrink = cap > settings().verify_keep_bytes && need < cap / 4;
   if (need <= cap && !shrink) return 0;
-  HIP_TRY(hipEventSynchronize(d.scratch_free));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (p) HIP_TRY(hipFree(p));
-  p = nullptr;
-  cap = 0;
-  HIP_TRY(hipMalloc(&p, need));
-  cap = need;
-  return 0;
+  return regrow(d, p, cap, need, &s, 0);
 }
 
 // The per-launch z_i seed: 32 bytes from the host's CSPRNG (dalek: merlin transcript + thread_rng),
@@ -1681,17 +1520,17 @@ int launch_straus(DevCtx& d, const uint8_t* dig, const uint32_t* mi, const uint8
                   uint64_t nvotes, uint64_t* leaf, hipStream_t s) {
   if (nvotes == 0) return 0;
   if (int rc = ensure_verify_tables(d)) return rc;
-  if (nvotes > verify_max_launch()) {
+  if (nvotes > settings().verify_max_launch) {
     // consecutive launches of at most NWC_VERIFY_MAX_LAUNCH votes, as launch_verify: sub-batches
     // are any consecutive votes (each reads its own certificate's digest through mi)
-    const uint64_t step = verify_max_launch();
+    const uint64_t step = settings().verify_max_launch;
     for (uint64_t lo = 0; lo < nvotes; lo += step)
       if (int rc = launch_straus(d, dig, mi + lo, pks + 32 * lo, sigs + 64 * lo, std::min(step, nvotes - lo), leaf + lo / 64, s))
         return rc;
     return 0;
   }
   if (!d.comb16)   // no basepoint comb (NWC_COMB16=0): the exact leaves
-    return launch_verify(d, dig, mi, 0, pks, sigs, nvotes, 0, leaf, s);
+    return launch_verify(d, {.msgs = dig, .msg_index = mi, .pks = pks, .sigs = sigs, .n = nvotes, .out_words = leaf, .stream = s});
   // sub-batches of ~12 votes (knobs().straus_nq), every lane slot the same number of rounds
   const uint32_t target = knobs().straus_nq.load();
   const uint64_t resident = (uint64_t)d.cus * nwc::STRAUS_WAVES_PER_SIMD * 256;
@@ -1735,15 +1574,15 @@ int launch_msm(DevCtx& d, const uint8_t* dig, const uint32_t* mi, const uint8_t*
                uint64_t nvotes, uint64_t* leaf, hipStream_t s) {
   if (nvotes == 0) return 0;
   if (int rc = ensure_verify_tables(d)) return rc;
-  if (nvotes > verify_max_launch()) {
-    const uint64_t step = verify_max_launch();
+  if (nvotes > settings().verify_max_launch) {
+    const uint64_t step = settings().verify_max_launch;
     for (uint64_t lo = 0; lo < nvotes; lo += step)
       if (int rc = launch_msm(d, dig, mi + lo, pks + 32 * lo, sigs + 64 * lo, std::min(step, nvotes - lo), leaf + lo / 64, s))
         return rc;
     return 0;
   }
   if (!d.comb16)   // no basepoint comb (NWC_COMB16=0): the exact leaves
-    return launch_verify(d, dig, mi, 0, pks, sigs, nvotes, 0, leaf, s);
+    return launch_verify(d, {.msgs = dig, .msg_index = mi, .pks = pks, .sigs = sigs, .n = nvotes, .out_words = leaf, .stream = s});
   static int bpc = [] {
     int b = 0;
     (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&b, reinterpret_cast<const void*>(nwc::k_verify_msm), 64, 0);
@@ -1814,7 +1653,7 @@ int launch_resolve(DevCtx& d, const uint8_t* dig, const uint32_t* mi, uint64_t m
   if (int rc = ensure_buf(d, d.rs_buf, d.rs_cap, state_off + align256(4 * (size_t)m), s)) return rc;
   // one lane per failing vote; a lane slot's ladder table lives in the verification scratch
   const uint64_t grid = (uint64_t)d.cus * d.verify_blocks_per_cu;
-  if (int rc = ensure_scratch(d, (size_t)grid * 256 * 2 * nwc::TAB_BYTES_PER_LANE, std::min(nv, verify_max_launch())))
+  if (int rc = ensure_scratch(d, (size_t)grid * 256 * 2 * nwc::TAB_BYTES_PER_LANE, std::min(nv, settings().verify_max_launch)))
     return rc;
   HIP_TRY(hipStreamWaitEvent(s, d.scratch_free, 0));
   uint32_t* const count = reinterpret_cast<uint32_t*>(d.rs_buf);
@@ -1850,14 +1689,11 @@ int launch_batch_dalek(DevCtx& d, const uint8_t* dig, const uint32_t* mi, uint64
   if (int rc = ensure_verify_tables(d)) return rc;
   const bool committee = d.cm_n && d.cm_comb;
   const bool lkeys = !d.cm_n && nv >= nwc::LK_MIN_EQUATIONS && knobs().launch_keys.load();
-  if (verify_path() != VPath::Default || !d.comb16 || !(committee || lkeys))
+  if (settings().verify_path != VPath::Default || !d.comb16 || !(committee || lkeys))
     return launch_msm(d, dig, mi, pks, sigs, nv, leaf, s);
-  if (int rc = launch_verify(d, dig, mi, 0, pks, sigs, nv, 0, leaf, s)) return rc;
-  const nwc::Committee cm = committee ? nwc::Committee{d.cm_keys, d.cm_flags, d.cm_tables, d.cm_comb, d.cm_slots,
-                                                       d.cm_slot_mask, d.cm_n}
-                                      : nwc::Committee{d.lk.keys, d.lk.flags, nullptr, d.lk.comb, d.lk.slots,
-                                                       nwc::LK_SLOTS - 1, nwc::LK_MAX_KEYS};
-  return launch_resolve(d, dig, mi, m, pks, sigs, nv, leaf, cm, s);
+  if (int rc = launch_verify(d, {.msgs = dig, .msg_index = mi, .pks = pks, .sigs = sigs, .n = nv, .out_words = leaf, .stream = s}))
+    return rc;
+  return launch_resolve(d, dig, mi, m, pks, sigs, nv, leaf, committee ? committee_of(d) : launch_committee_of(d), s);
 }
 
 // Per-vote leaf bits of every device's share (whole certificates) -> certificate verdicts and the
@@ -2196,7 +2032,7 @@ int nwc_verify_batch_many(const uint8_t* digests, const uint32_t* offsets, const
   for (int r : rc) if (r < 0) return r;
   const auto t2 = clk::now();
   const int r = batch_verdicts(offsets, m, cuts, parts, cert_ok_bitmap, bad_vote_bitmap);
-  if (host_timing()) {
+  if (settings().host_timing) {
     auto ms = [](clk::duration d) { return std::chrono::duration<double>(d).count() * 1e3; };
     std::fprintf(stderr, "nwc_verify_batch_many: %zu certificates, %llu votes: devices %.2f ms, verdicts %.2f ms\n",
                  m, (unsigned long long)nv, ms(t2 - t1), ms(clk::now() - t2));
@@ -2357,7 +2193,7 @@ int nwc_auto_cache_info(uint32_t* capacity, uint64_t* builds, uint64_t* hits) {
   if (int rc = require_init()) return rc;
   DevCtx& d = *ctx(t_dev < (int)g_devs.size() ? t_dev : 0);
   std::lock_guard<std::mutex> lk(d.mu);
-  if (capacity) *capacity = auto_keys_cap();
+  if (capacity) *capacity = settings().auto_keys;
   if (builds) *builds = d.ak_builds;
   if (hits) *hits = d.ak_hits;
   return 0;
@@ -2438,8 +2274,9 @@ int nwc_dev_verify(const void* d_msgs, const void* d_msg_index, uint64_t msg_str
                    const void* d_sigs, uint64_t n, int strict, void* d_verdict_words, void* stream) {
   DEV_PROLOGUE
   if (n && (!d_msgs || !d_pks || !d_sigs || !d_verdict_words)) return set_err(NWC_ERR_ARG, "null buffer");
-  return launch_verify(d, (const uint8_t*)d_msgs, (const uint32_t*)d_msg_index, msg_stride, (const uint8_t*)d_pks,
-                       (const uint8_t*)d_sigs, n, strict, (uint64_t*)d_verdict_words, s);
+  return launch_verify(d, {.msgs = (const uint8_t*)d_msgs, .msg_index = (const uint32_t*)d_msg_index, .msg_stride = msg_stride,
+                           .pks = (const uint8_t*)d_pks, .sigs = (const uint8_t*)d_sigs, .n = n, .strict = strict,
+                           .out_words = (uint64_t*)d_verdict_words, .stream = s});
 }
 
 int nwc_diag_verify_clock(const void* d_msgs, uint64_t msg_stride, const void* d_pks, const void* d_sigs, uint64_t n,
@@ -2450,14 +2287,15 @@ int nwc_diag_verify_clock(const void* d_msgs, uint64_t msg_stride, const void* d
   // the stamps come from the plain k_verify launch: a committee cache would send these strict
   // equations to the comb kernel (no stamps), and a split launch would overwrite them
   if (d.cm_n) return set_err(NWC_ERR_ARG, "the clock stamp needs the plain k_verify path: clear the committee cache first");
-  if (n > verify_max_launch())
-    return set_err(NWC_ERR_ARG, "the clock stamp needs a single launch (n <= %llu)", (unsigned long long)verify_max_launch());
+  if (n > settings().verify_max_launch)
+    return set_err(NWC_ERR_ARG, "the clock stamp needs a single launch (n <= %llu)", (unsigned long long)settings().verify_max_launch);
   // one stamp slot per wave of the largest grid launch_verify gives k_verify
   const uint64_t nwaves = (uint64_t)d.cus * d.verify_blocks_per_cu * NWC_VERIFY_GRID_MULT * 4;
   if (!d.stamps) HIP_TRY(hipMalloc(&d.stamps, 32 * nwaves));
   HIP_TRY(hipMemsetAsync(d.stamps, 0, 32 * nwaves, s));
-  if (int rc = launch_verify(d, (const uint8_t*)d_msgs, nullptr, msg_stride, (const uint8_t*)d_pks, (const uint8_t*)d_sigs,
-                             n, 1, (uint64_t*)d_verdict_words, s, LV_STAMP))
+  if (int rc = launch_verify(d, {.msgs = (const uint8_t*)d_msgs, .msg_stride = msg_stride, .pks = (const uint8_t*)d_pks,
+                                 .sigs = (const uint8_t*)d_sigs, .n = n, .strict = 1, .out_words = (uint64_t*)d_verdict_words,
+                                 .stream = s, .flags = LV_STAMP}))
     return rc;
   std::vector<uint64_t> st(4 * nwaves);
   HIP_TRY(hipMemcpyAsync(st.data(), d.stamps, 32 * nwaves, hipMemcpyDeviceToHost, s));
@@ -2662,21 +2500,13 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
   // inversion per vote.  NWC_SIGN_DEFER=0: k_verify_comb per chunk (A/B).
   const bool chunked = nch > 1;
   const bool defer = chunked && deferrable_list(d);
-  const bool ysplit = defer && sign_defer();
+  const bool ysplit = defer && settings().sign_defer;
   const size_t need = align256(total + 128 * (m + 2)) + align256(32 * m) * 3 + align256(64 * m) + align256(32 * vt) +
                       align256(64 * vt) + align256(4 * vt) + align256(4) + align256(4 * m) + align256(16 * m) +
                       align256(4 * m) + align256(8 * ((m + 63) / 64)) + align256(8 * ((vt + 63) / 64)) +
                       (ysplit ? 3 * align256(32 * vt) + align256(4 * vt) + 3 * align256(32 * m) + align256(4 * m) : 0);
-  if (need > d.msg_arena_cap) {
-    HIP_TRY(hipEventSynchronize(d.scratch_free));
-    HIP_TRY(hipStreamSynchronize(s));
-    if (d.msg_arena) HIP_TRY(hipFree(d.msg_arena));
-    d.msg_arena = nullptr;
-    d.msg_arena_cap = 0;
-    const size_t cap = need + need / 4 + (1 << 20);
-    HIP_TRY(hipMalloc(&d.msg_arena, cap));
-    d.msg_arena_cap = cap;
-  }
+  if (need > d.msg_arena_cap)
+    if (int rc = regrow(d, d.msg_arena, d.msg_arena_cap, need, &s, need / 4 + (1 << 20))) return rc;
   Carve c(d.msg_arena);
   nwc::MsgArgs a{};   // the whole call's arrays
   a.data = ddata;
@@ -2724,11 +2554,7 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
   if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
   if (4 * nch > (64u << 10)) return set_err(NWC_ERR_ARG, "too many chunks");   // counts below sanitize_range's offsets
   uint32_t* nv_host = reinterpret_cast<uint32_t*>(d.pinned);   // pinned: the count copies stay asynchronous
-  while (d.ev_cnt.size() < nch) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    d.ev_cnt.push_back(e);
-  }
+  if (int rc = ensure_events(d.ev_cnt, nch)) return rc;
   // the leaf stream when chunks overlap: the side stream, which has a hardware queue of its own
   // (GPU_MAX_HW_QUEUES = 4: a stream created later shared the transfer stream's queue, and its
   // leaves waited behind the markers of the in-flight copies, profiles/r05/wire_host.md)
@@ -2746,11 +2572,11 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
   bool pending = false;   // deferred leaf launches whose list passes have not been queued
   HIP_TRY(hipMemsetAsync(a.v_total, 0, 4, s));
   HIP_TRY(hipMemsetAsync(a.v_msg, 0, 4 * vt, s));
-  const nwc::Committee cm{d.cm_keys, d.cm_flags, d.cm_tables, d.cm_comb, d.cm_slots, d.cm_slot_mask, d.cm_n};
+  const nwc::Committee cm = committee_of(d);
   const nwc::CommitteeCfg cc{d.cc_stakes, d.cc_worker_off, d.cc_worker_ids, d.cc_quorum, d.cc_n};
   const size_t first_lds = 4 * (size_t)std::max<uint32_t>(1, std::min<uint32_t>(d.cc_n, nwc::MSG_MAX_COMMITTEE));
   // NWC_HOST_TIMING: host-side stamps of the steps (which call waits on what)
-  const bool timing = host_timing();
+  const bool timing = settings().host_timing;
   const auto tm0 = std::chrono::steady_clock::now();
   std::vector<std::pair<const char*, double>> marks;
   auto mark = [&](const char* what) {
@@ -2772,9 +2598,10 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
     const bool y = deferred && ysplit;
     const nwc::SignPass sp{sr, owed_lo, owed_hi - owed_lo, lbits, comb_sign_blocks(d, owed_hi - owed_lo)};
     const nwc::SignRecs srl = sign_recs_at(sr, (int64_t)v0);
-    if (int rc = launch_verify(d, a.cdig, a.v_msg + v0, 0, a.v_pk + 32 * v0, a.v_sig + 64 * v0, upto - v0, 0,
-                               lbits + v0 / 64, ls, deferred ? LV_DEFER_LIST : 0, nullptr, v0, nullptr,
-                               y ? &srl : nullptr, y ? &sp : nullptr))
+    if (int rc = launch_verify(d, {.msgs = a.cdig, .msg_index = a.v_msg + v0, .pks = a.v_pk + 32 * v0, .sigs = a.v_sig + 64 * v0,
+                                   .n = upto - v0, .out_words = lbits + v0 / 64, .stream = ls,
+                                   .flags = deferred ? LV_DEFER_LIST : 0, .list_base = v0, .sign_recs = y ? &srl : nullptr,
+                                   .sign_pass = y ? &sp : nullptr}))
       return rc;
     if (y) {
       owed_lo = v0;
@@ -2817,8 +2644,8 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
     }
     if (int rc = finish()) return rc;
     list_dirty = true;
-    return launch_verify(d, a.eq_msg + 32 * c0, nullptr, 1, a.eq_pk + 32 * c0, a.eq_sig + 64 * c0, c1 - c0, 1,
-                         sbits + c0 / 64, ls);
+    return launch_verify(d, {.msgs = a.eq_msg + 32 * c0, .msg_stride = 1, .pks = a.eq_pk + 32 * c0, .sigs = a.eq_sig + 64 * c0,
+                             .n = c1 - c0, .strict = 1, .out_words = sbits + c0 / 64, .stream = ls});
   };
   // The strict equations of the first chunks go in one launch after chunk strict_at's leaves,
   // early, where the leaf stream has slack to absorb its ~0.17 ms (a latency-bound launch); the
@@ -2828,7 +2655,7 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
   bool aligned = true;
   for (size_t k = 1; k < nch; ++k) aligned = aligned && (cuts[k] & 63) == 0;
   const size_t strict_at = aligned && nch >= 3 ? nch / 3 : (nch >= 2 ? nch - 2 : 0);   // its iteration k
-  strict_y = ysplit && aligned && g_cm_is_config.load() && strict_y_on();
+  strict_y = ysplit && aligned && g_cm_is_config.load() && settings().strict_y;
   size_t strict_done = 0;   // messages [0, strict_done) have their strict launch queued
   uint64_t nv = 0;
   size_t queued = 0;   // chunks whose parse is queued
@@ -2909,7 +2736,9 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
   } else {
     // one chunk: the strict launch (it needs no count) queued before the host waits for the
     // count, the Header::digest checks beside the leaves on the side stream
-    if (int rc = launch_verify(d, a.eq_msg, nullptr, 1, a.eq_pk, a.eq_sig, m, 1, sbits, s)) return rc;
+    if (int rc = launch_verify(d, {.msgs = a.eq_msg, .msg_stride = 1, .pks = a.eq_pk, .sigs = a.eq_sig, .n = m, .strict = 1,
+                                   .out_words = sbits, .stream = s}))
+      return rc;
     HIP_TRY(hipEventRecord(d.ev_fork, s));
     HIP_TRY(hipStreamWaitEvent(d.side, d.ev_fork, 0));
     hipLaunchKernelGGL(nwc::k_header_digests, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, d.side, a);
@@ -2975,10 +2804,7 @@ static int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, 
   // parsed and verified while chunk k + 1 crosses PCIe.  The chunks share the message offsets
   // (uploaded first, relative to ddata) and the message arena (sanitize_dev, run per chunk in
   // stream order).
-  static const uint64_t msg_chunk = [] {
-    const char* e = std::getenv("NWC_MSG_CHUNK");   // 0 = one copy, then one pass (A/B)
-    return e ? (uint64_t)std::strtoull(e, nullptr, 10) : (uint64_t)NWC_MSG_CHUNK;
-  }();
+  const uint64_t msg_chunk = settings().msg_chunk;   // 0 = one copy, then one pass (A/B)
   // chunk sizes: from 16 MB doubling up to msg_chunk, and never more than half of what remains
   // (>= 8 MB, so the last one is <= 16 MB): the first parse starts after a short copy, and the
   // work left when the last copy lands (that chunk's parse, leaves and strict equations, the
@@ -3024,11 +2850,7 @@ static int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, 
       return rc;
   } else {
     if (int rc = ensure_stager(d)) return rc;
-    while (d.ev_chunk.size() < nch) {
-      hipEvent_t e;
-      HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      d.ev_chunk.push_back(e);
-    }
+    if (int rc = ensure_events(d.ev_chunk, nch)) return rc;
     // the copies wait for every launch that may still read the arena
     HIP_TRY(hipEventRecord(d.ev_fork, d.stream));
     HIP_TRY(hipStreamWaitEvent(d.xfer, d.ev_fork, 0));
@@ -3076,7 +2898,7 @@ static int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, 
       (void)hipStreamSynchronize(d.xfer);   // no copy still writes the arena when the call returns
       return rc;
     }
-    if (host_timing()) {
+    if (settings().host_timing) {
       HIP_TRY(hipStreamSynchronize(d.stream));
       const auto tm1 = std::chrono::steady_clock::now();
       std::fprintf(stderr, "nwc sanitize: %zu messages, %.1f MB in %zu chunks: copies queued after %.2f ms, pipeline done %.2f ms later\n",

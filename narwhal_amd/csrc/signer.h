@@ -70,22 +70,14 @@ int expand_key(DevCtx& d, const uint8_t* seed, const uint8_t* pub, nwc::SignKey*
   return 0;
 }
 
-// n <= this takes k_sign_wide under "sign_path" 0 (by size).  Default 256, from measurement on an
+// n <= NWC_SIGN_WIDE_MAX takes k_sign_wide under "sign_path" 0 (by size).  Default 256, from measurement on an
 // MI355X (tools/sign_rate.py, profiles/sign/sign_rate.json, DESIGN.md "Signing"): the wide kernel's
 // host-call p50 is below the lane kernel's by more than the run-to-run spread at every measured
 // n <= 256 (90 us against 408 us at n = 1, 281 us against 379 us at n = 256) and above it at 1,024
 // (440 us against 396 us).
-uint64_t sign_wide_max() {
-  static const uint64_t v = [] {
-    const char* e = std::getenv("NWC_SIGN_WIDE_MAX");
-    return e ? std::strtoull(e, nullptr, 10) : 256ull;
-  }();
-  return v;
-}
-
 bool sign_takes_wide(uint64_t n) {
   const uint32_t path = knobs().sign_path;
-  return path == 2 || (path == 0 && n <= sign_wide_max());
+  return path == 2 || (path == 0 && n <= settings().sign_wide_max);
 }
 
 int launch_sign(DevCtx& d, const nwc::SignKey* key, const uint8_t* msgs, uint64_t stride, uint64_t n, uint8_t* sigs,
@@ -192,10 +184,7 @@ int nwc_signer_sign_many(void* signer, const uint8_t* msgs32, size_t n, uint8_t*
   std::lock_guard<std::mutex> lk(d.mu);
   HIP_TRY(hipSetDevice(d.hip_id));
   if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
-  static const bool spin = [] {
-    const char* e = std::getenv("NWC_SPIN_WAIT");   // 0 = wait for the stream (A/B)
-    return !(e && std::strcmp(e, "0") == 0);
-  }();
+  const bool spin = settings().spin_wait;   // 0 = wait for the stream (A/B)
   const bool wide = sign_takes_wide(n);
   for (uint64_t lo = 0; lo < n; lo += SIGN_HOST_CHUNK) {
     const uint64_t c = std::min<uint64_t>(SIGN_HOST_CHUNK, n - lo);
@@ -204,26 +193,13 @@ int nwc_signer_sign_many(void* signer, const uint8_t* msgs32, size_t n, uint8_t*
     std::memcpy(h, msgs32 + 32 * lo, 32 * c);
     std::memset(h + fo, 0, c);
     if (int rc = launch_sign(d, sg.key, d.pinned_dev, 32, c, d.pinned_dev + so, d.pinned_dev + fo, wide, d.stream)) return rc;
-    if (spin && c <= NWC_WIDE_MAX) {
-      // poll the "written" bytes (stored after the signature's words and a system fence); a launch
-      // that never writes them (a device error) falls back to the stream wait after 200 ms
-      const volatile uint8_t* vb = h + fo;
-      const auto t0 = std::chrono::steady_clock::now();
-      uint64_t done = 0;
-      for (;;) {
-        while (done < c && (vb[done] & 0x80u)) ++done;
-        if (done == c) break;
-        if (std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-          HIP_TRY(hipStreamSynchronize(d.stream));
-          for (done = 0; done < c && (vb[done] & 0x80u); ++done) {}
-          if (done != c) return set_err(NWC_ERR_DEVICE, "sign kernel left signatures unwritten");
-          break;
-        }
-        __builtin_ia32_pause();
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    } else {
+    // poll the "written" bytes (stored after the signature's words and a system fence); a launch
+    // that never writes them (a device error) falls back to the stream wait after 200 ms
+    const bool poll = spin && c <= NWC_WIDE_MAX;
+    if (!poll || !nwc::plan::poll_written(h + fo, c, std::chrono::milliseconds(200))) {
       HIP_TRY(hipStreamSynchronize(d.stream));
+      if (poll && !nwc::plan::poll_written(h + fo, c, std::chrono::microseconds(0)))
+        return set_err(NWC_ERR_DEVICE, "sign kernel left signatures unwritten");
     }
     std::memcpy(sigs + 64 * lo, h + so, 64 * c);
   }

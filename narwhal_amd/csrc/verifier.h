@@ -14,9 +14,6 @@
 
 namespace {
 
-#ifndef NWC_VERIFIER_GROUP_EQ
-#define NWC_VERIFIER_GROUP_EQ 4096
-#endif
 constexpr int VERIFIER_BUFFERS = 2;   // one group in flight, the next one filling
 
 struct Verifier final : nwc::vq::Backend {
@@ -90,14 +87,14 @@ struct Verifier final : nwc::vq::Backend {
                       dc.scratch, dc.fb_list, dc.fb_count, 0u, nwc::Committee{}};
     const nwc::CombArgs ca{nullptr, nullptr, dc.comb_base, dc.comb16, nullptr};
     if (ncm) {
-      a.committee = nwc::Committee{dc.cm_keys, dc.cm_flags, dc.cm_tables, dc.cm_comb, dc.cm_slots, dc.cm_slot_mask, dc.cm_n};
+      a.committee = committee_of(dc);
       hipLaunchKernelGGL(nwc::k_verify_group_wide, dim3(ncm), dim3(128), 0, dc.stream, a, ca,
                          nwc::GroupArgs{g.lists, g.modes, g.vbytes, ncm});
       HIP_TRY(hipGetLastError());
     }
     if (nak) {
       ++dc.ak_hits;
-      a.committee = nwc::Committee{dc.ak_keys, dc.ak_flags, dc.ak_tables, dc.ak_comb, dc.ak_slots, dc.ak_host.mask, dc.ak_n};
+      a.committee = auto_committee_of(dc);
       hipLaunchKernelGGL(nwc::k_verify_group_wide, dim3(nak), dim3(128), 0, dc.stream, a, ca,
                          nwc::GroupArgs{g.lists + ncm, g.modes, g.vbytes, nak});
       HIP_TRY(hipGetLastError());
@@ -109,7 +106,7 @@ struct Verifier final : nwc::vq::Backend {
         HIP_TRY(hipStreamWaitEvent(dc.side, dc.ev_fork, 0));
       }
       a.committee = nwc::Committee{};
-      a.force_fb_every = force_fallback_every();
+      a.force_fb_every = settings().force_fallback_every;
       hipLaunchKernelGGL(nwc::k_verify_group_cold, dim3(ncold), dim3(256), 0, dc.side, a,
                          (const nwc::ge_niels_pad*)dc.comb16, nwc::GroupArgs{g.lists + cap, g.modes, g.vbytes, ncold});
       HIP_TRY(hipGetLastError());
@@ -157,7 +154,9 @@ struct Verifier final : nwc::vq::Backend {
     const size_t out_off = (size_t)((uint8_t*)dout - dc.arena);
     std::memset(s + out_off, 0, 8 * (words + 1));
     HIP_TRY(hipMemcpyAsync(dc.arena, s, out_off + 8 * (words + 1), hipMemcpyHostToDevice, dc.stream));
-    if (int rc = launch_verify(dc, dm, nullptr, 1, dp, ds, m, strict ? 1 : 0, dout, dc.stream, LV_OUT_ZEROED)) return rc;
+    if (int rc = launch_verify(dc, {.msgs = dm, .msg_stride = 1, .pks = dp, .sigs = ds, .n = m, .strict = strict ? 1 : 0,
+                                    .out_words = dout, .stream = dc.stream, .flags = LV_OUT_ZEROED}))
+      return rc;
     HIP_TRY(hipMemcpyAsync(s, dout, 8 * words, hipMemcpyDeviceToHost, dc.stream));
     HIP_TRY(hipStreamSynchronize(dc.stream));
     const uint64_t* w = reinterpret_cast<const uint64_t*>(s);
@@ -207,15 +206,6 @@ struct Verifier final : nwc::vq::Backend {
 std::mutex g_ver_mu;   // guards g_verifiers; taken after g_mu, never with a context's mu held
 std::unordered_set<Verifier*> g_verifiers;
 
-uint32_t verifier_group_eq() {
-  static const uint32_t v = [] {
-    const char* e = std::getenv("NWC_VERIFIER_GROUP_EQ");
-    const unsigned long x = e ? std::strtoul(e, nullptr, 10) : (unsigned long)NWC_VERIFIER_GROUP_EQ;
-    return (uint32_t)std::min<unsigned long>(std::max<unsigned long>(x, 1), 1ul << 16);
-  }();
-  return v;
-}
-
 // Stops a verifier's queue (queued requests finish, blocked callers are woken and leave) and frees
 // its buffers once the streams have passed them.  Caller holds g_mu.
 void verifier_retire(Verifier& v) {
@@ -261,11 +251,11 @@ void* nwc_verifier_create(uint32_t max_requests, uint32_t max_wait_us) {
   auto v = std::make_unique<Verifier>();
   v->d = dp;
   v->di = di;
-  v->cap = verifier_group_eq();
+  v->cap = settings().verifier_group_eq;
   v->max_req = max_requests == 0 || max_requests > v->cap ? v->cap : max_requests;
   // the first-sight kernel needs the basepoint comb, and the A/B paths (NWC_VERIFY_PATH, NWC_COLD=0)
   // are the plain entries' business
-  v->grouping = cold_path() && verify_path() == VPath::Default;
+  v->grouping = settings().cold && settings().verify_path == VPath::Default;
   v->layout();
   if (v->grouping) {
     std::lock_guard<std::mutex> lk(dp->mu);

@@ -59,11 +59,15 @@ def test_strict_many_host_ragged(oracle):
 @pytest.mark.parametrize("env", [{"NWC_HOST_PAIR_FIRST": "4096", "NWC_HOST_PAIR_GROWTH": "2"},
                                  {"NWC_HOST_PAIR_FIRST": "8192", "NWC_HOST_PAIR_GROWTH": "1",
                                   "NWC_FORCE_FALLBACK_EVERY": "3"},
-                                 {"NWC_HOST_PAIR": "0"}])
+                                 {"NWC_HOST_PAIR": "0"},
+                                 {"NWC_HOST_PAIR": "0", "NWC_HOST_CHUNK": "4096", "NWC_HOST_CHUNK_GROWTH": "2",
+                                  "NWC_HOST_CHUNK_MAX": "10000"}])
 def test_strict_many_host_pipelines(env, oracle, tmp_path):
     """Strict host calls through the paired pipeline cut into many alternating chunks (each chunk
     on its own half of the table slots and its own fallback list; one case sends every third
-    equation of each chunk through the fallback kernel) and through the single-stream chunks:
+    equation of each chunk through the fallback kernel) and through the single-stream chunks
+    (one case with a largest chunk that is no multiple of 64: it is rounded down to 9,984, so
+    every chunk still starts on a verdict word):
     verdicts equal the oracle's, on two calls in a row.  Each case in its own process (libnwc
     reads the switches once)."""
     import os
