@@ -28,6 +28,7 @@
 
 #include "nwc.h"
 #include "copy_pool.h"
+#include "dev_buf.h"
 #include "kernels.hip"
 #include "launch_keys.h"
 #include "messages.h"
@@ -116,6 +117,39 @@ uint32_t build_slots(const std::vector<nwc::u32>& keys, size_t n, std::vector<in
   }
 }
 
+// The runtime's allocation calls, for dev_buf.h: the only place in this file that frees.
+struct HipAlloc {
+  using Error = hipError_t;
+  using Stream = hipStream_t;
+  static constexpr Error ok = hipSuccess;
+  static Error alloc(void** p, size_t bytes) { return hipMalloc(p, bytes); }
+  static Error alloc_async(void** p, size_t bytes, Stream s) { return hipMallocAsync(p, bytes, s); }
+  static Error alloc_pinned(void** host, void** dev, size_t bytes) {
+    // coherent: a kernel's stores reach the host while it polls them
+    if (Error e = hipHostMalloc(host, bytes, hipHostMallocCoherent)) return e;
+    const Error e = hipHostGetDevicePointer(dev, *host, 0);
+    if (e != hipSuccess) (void)hipHostFree(*host);
+    return e;
+  }
+  static Error free(void* p) { return hipFree(p); }
+  static Error free_async(void* p, Stream s) { return hipFreeAsync(p, s); }
+  static Error free_pinned(void* p) { return hipHostFree(p); }
+};
+template <class T> using Buf = nwc::buf::Buf<T, HipAlloc>;
+using RawBuf = nwc::buf::RawBuf<HipAlloc>;
+using nwc::buf::Account;
+using nwc::buf::Keep;
+using nwc::buf::Trimmable;
+// Plain release of each buffer; the first error, after all of them are empty.
+hipError_t release_each(std::initializer_list<RawBuf*> bufs) {
+  hipError_t first = hipSuccess;
+  for (RawBuf* b : bufs)
+    if (hipError_t e = b->release(); first == hipSuccess) first = e;
+  return first;
+}
+
+// Every device and pinned buffer is a Buf registered with `bufs` (dev_buf.h) under the account
+// nwc_memory_info reports it in, Trimmable if nwc_trim drops it.
 struct DevCtx {
   int hip_id = 0;
   int cus = 0;
@@ -130,78 +164,70 @@ struct DevCtx {
   hipStream_t xfer = nullptr;
   std::vector<hipEvent_t> ev_chunk;
   std::vector<hipEvent_t> ev_cnt;      // sanitize: chunk k's vote count copied to the host
-  nwc::ge_niels* base_table = nullptr;
-  nwc::ge_niels* sign_table = nullptr;   // the signers' basepoint table (60 KB, sign.h), built by the first signer
-  nwc::ge_niels_pad* base24 = nullptr;   // radix-2^24 basepoint tables (2.1 GB)
-  nwc::ge_p3* base24_points = nullptr;    // B and 2^141 B
-  nwc::ge_niels_pad* comb_base = nullptr;   // radix-256 basepoint comb (528 KB): latency kernel
-  nwc::ge_niels_pad* comb16 = nullptr;      // basepoint comb (radix 2^NWC_BCOMB_BITS, 67 MB at 2^16): k_verify_comb
-  nwc::ge_p3* comb16_bases = nullptr;       // its window bases 2^(bits w) B (built at init)
-  nwc::ge_p3* kb_bases = nullptr;           // key comb window bases (scratch of build_key_combs)
+  nwc::buf::BufSet<HipAlloc> bufs;     // owns every Buf below
+  Buf<nwc::ge_niels> base_table{bufs, Account::Tables, Keep};
+  Buf<nwc::ge_niels> sign_table{bufs, Account::Tables, Keep};   // the signers' basepoint table (60 KB, sign.h), built by the first signer
+  Buf<nwc::ge_niels_pad> base24{bufs, Account::Tables, Keep};   // radix-2^24 basepoint tables (2.1 GB)
+  Buf<nwc::ge_p3> base24_points{bufs, Account::Tables, Keep};   // B and 2^141 B
+  Buf<nwc::ge_niels_pad> comb_base{bufs, Account::Tables, Keep};   // radix-256 basepoint comb (528 KB): latency kernel
+  Buf<nwc::ge_niels_pad> comb16{bufs, Account::Tables, Keep};      // basepoint comb (radix 2^NWC_BCOMB_BITS, 67 MB at 2^16): k_verify_comb
+  Buf<nwc::ge_p3> comb16_bases{bufs, Account::Tables, Keep};       // its window bases 2^(bits w) B (built at init)
+  Buf<nwc::ge_p3> kb_bases{bufs, Account::AutoCache, Keep};        // key comb window bases (scratch of build_key_combs)
   size_t kb_cap = 0;
   int comb_blocks_per_cu = 1;
-  uint8_t* straus_scratch = nullptr;   // k_verify_straus per-lane tables (nwc_dev_verify_batch_straus)
-  size_t straus_cap = 0;
-  uint8_t* msm_scratch = nullptr;      // k_verify_msm per-wave points and digits (nwc_dev_verify_batch_msm)
-  size_t msm_cap = 0;
-  uint32_t* msm_stats = nullptr;       // groups passed / failed / key overflow (nwc_msm_stats)
-  uint8_t* rs_buf = nullptr;           // dalek's equation per certificate (resolve.h): failing-vote list, certificate states
-  size_t rs_cap = 0;
-  uint32_t* uc_list = nullptr;     // k_verify_comb: equations whose key is not cached
-  uint32_t* uc_count = nullptr;
+  Buf<uint8_t> straus_scratch{bufs, Account::Scratch, Trimmable};   // k_verify_straus per-lane tables (nwc_dev_verify_batch_straus)
+  Buf<uint8_t> msm_scratch{bufs, Account::Scratch, Trimmable};      // k_verify_msm per-wave points and digits (nwc_dev_verify_batch_msm)
+  Buf<uint32_t> msm_stats{bufs, Account::Uncounted, Keep};          // groups passed / failed / key overflow (nwc_msm_stats)
+  Buf<uint8_t> rs_buf{bufs, Account::Scratch, Trimmable};           // dalek's equation per certificate (resolve.h): failing-vote list, certificate states
+  Buf<uint32_t> uc_list{bufs, Account::Scratch, Trimmable};     // k_verify_comb: equations whose key is not cached
+  Buf<uint32_t> uc_count{bufs, Account::Uncounted, Keep};
   bool hold_lists = false;         // a call with a deferred list pending: ensure_scratch does not shrink the lists
   bool tables_ready = false;       // ensure_verify_tables has built the basepoint tables, memo and auto cache
   // k_verify per-lane table slots; reused by every launch, so launches that use it are
   // serialised across streams with `scratch_free` (recorded after each such launch).
-  uint8_t* scratch = nullptr;
-  size_t scratch_cap = 0;
-  uint32_t* fb_list = nullptr;     // lanes whose half-size reduction failed (k_verify_fallback)
-  uint32_t* fb_count = nullptr;
-  uint8_t* pair_buf = nullptr;      // the paired strict host pipeline: per-chunk fallback counts + lists
-  size_t pair_cap = 0;
-  uint8_t* sign_buf = nullptr;      // large host calls on the comb path: two chunks' SignRecs
-  size_t sign_cap = 0;
+  Buf<uint8_t> scratch{bufs, Account::Scratch, Trimmable};
+  Buf<uint32_t> fb_list{bufs, Account::Scratch, Trimmable};     // lanes whose half-size reduction failed (k_verify_fallback)
+  Buf<uint32_t> fb_count{bufs, Account::Uncounted, Keep};
+  Buf<uint8_t> pair_buf{bufs, Account::Scratch, Trimmable};     // the paired strict host pipeline: per-chunk fallback counts + lists
+  Buf<uint8_t> sign_buf{bufs, Account::Scratch, Trimmable};     // large host calls on the comb path: two chunks' SignRecs
   const uint8_t* busy_buf = nullptr;   // a buffer a host pipeline's launches use: never released under it
-  uint64_t* stamps = nullptr;      // k_verify<.., STAMP>: 4 words per wave of the resident grid (nwc_diag_verify_clock)
-  size_t fb_cap = 0;
+  Buf<uint64_t> stamps{bufs, Account::Uncounted, Keep};   // k_verify<.., STAMP>: 4 words per wave of the resident grid (nwc_diag_verify_clock)
+  size_t fb_cap = 0;               // entries of fb_list, uc_list and ts_uniq
   hipEvent_t scratch_free = nullptr;
   // batch-leaf torsion post-pass (k_tors_*): key hash set sized for fb_cap equations
-  int32_t* ts_slots = nullptr;
-  uint32_t* ts_flag = nullptr;
-  uint32_t* ts_uniq = nullptr;
-  uint32_t* ts_nuniq = nullptr;
+  Buf<int32_t> ts_slots{bufs, Account::Scratch, Trimmable};
+  Buf<uint32_t> ts_flag{bufs, Account::Scratch, Trimmable};
+  Buf<uint32_t> ts_uniq{bufs, Account::Scratch, Trimmable};
+  Buf<uint32_t> ts_nuniq{bufs, Account::Uncounted, Keep};
   uint32_t ts_slot_count = 0;
-  nwc::u32* km_keys = nullptr;   // torsion memo of uncached keys (KeyMemo), kept for the context's life
-  nwc::u32* km_flag = nullptr;
+  Buf<nwc::u32> km_keys{bufs, Account::Tables, Keep};   // torsion memo of uncached keys (KeyMemo), kept for the context's life
+  Buf<nwc::u32> km_flag{bufs, Account::Tables, Keep};
   // committee key cache (nwc_set_committee); buffers replaced only after scratch_free
-  nwc::u32* cm_keys = nullptr;
-  nwc::u32* cm_flags = nullptr;
-  nwc::ge_niels* cm_tables = nullptr;
-  nwc::ge_niels_pad* cm_comb = nullptr;   // per-key combs (committees of <= COMB_MAX_KEYS keys)
-  int32_t* cm_slots = nullptr;
+  Buf<nwc::u32> cm_keys{bufs, Account::Committee, Keep};
+  Buf<nwc::u32> cm_flags{bufs, Account::Committee, Keep};
+  Buf<nwc::ge_niels> cm_tables{bufs, Account::Committee, Keep};
+  Buf<nwc::ge_niels_pad> cm_comb{bufs, Account::Committee, Keep};   // per-key combs (committees of <= COMB_MAX_KEYS keys)
+  Buf<int32_t> cm_slots{bufs, Account::Committee, Keep};
   uint32_t cm_n = 0, cm_slot_mask = 0;
-  size_t cm_bytes = 0;                  // device bytes of the committee cache (nwc_memory_info)
-  uint8_t* arena = nullptr;
-  size_t arena_cap = 0;
+  Buf<uint8_t> arena{bufs, Account::Scratch, Trimmable};
   // config::Committee stake / worker tables (nwc_set_committee_config)
-  uint64_t* cc_stakes = nullptr;
-  uint32_t* cc_worker_off = nullptr;
-  uint32_t* cc_worker_ids = nullptr;
+  Buf<uint64_t> cc_stakes{bufs, Account::Uncounted, Keep};
+  Buf<uint32_t> cc_worker_off{bufs, Account::Uncounted, Keep};
+  Buf<uint32_t> cc_worker_ids{bufs, Account::Uncounted, Keep};
   uint64_t cc_quorum = 0;
   uint32_t cc_n = 0;
-  uint8_t* msg_arena = nullptr;   // nwc_sanitize_messages buffers
-  size_t msg_arena_cap = 0;
-  uint8_t* pinned = nullptr;   // host staging for small calls: one H2D and one D2H per call, or
-  uint8_t* pinned_dev = nullptr;   // read in place by the latency kernel through this device pointer
-  size_t pinned_cap = 0;
+  Buf<uint8_t> msg_arena{bufs, Account::Scratch, Trimmable};   // nwc_sanitize_messages buffers
+  // host staging for small calls: one H2D and one D2H per call, or read in place by the latency
+  // kernel through its device alias (dev())
+  Buf<uint8_t> pinned{bufs, Account::Uncounted, Keep, nwc::buf::Kind::Pinned};
   // auto key cache (NWC_AUTO_KEYS): keys of small host calls outside the committee cache, added
   // with their flags, 129-entry tables and combs the second time they are seen, so that repeated
   // first-sight certificates take the latency kernel; append-only, guarded by mu like the rest
-  nwc::u32* ak_keys = nullptr;
-  nwc::u32* ak_flags = nullptr;
-  nwc::ge_niels* ak_tables = nullptr;
-  nwc::ge_niels_pad* ak_comb = nullptr;
-  int32_t* ak_slots = nullptr;
+  Buf<nwc::u32> ak_keys{bufs, Account::AutoCache, Keep};
+  Buf<nwc::u32> ak_flags{bufs, Account::AutoCache, Keep};
+  Buf<nwc::ge_niels> ak_tables{bufs, Account::AutoCache, Keep};
+  Buf<nwc::ge_niels_pad> ak_comb{bufs, Account::AutoCache, Keep};
+  Buf<int32_t> ak_slots{bufs, Account::AutoCache, Keep};
   uint32_t ak_n = 0, ak_cap = 0, ak_slot_cap = 0;
   uint32_t ak_evict = 0;                  // next FIFO position once the cache is full
   uint64_t ak_builds = 0, ak_hits = 0;    // insert batches built / calls served from the auto cache
@@ -211,34 +237,24 @@ struct DevCtx {
   std::vector<nwc::u32> ak_pend_keys;
   std::vector<int32_t> ak_pend_slots;
   bool ak_pending = false;
-  // launch keys (launch_keys.h): allocated by the first large batch-leaf launch without a committee
+  // launch keys (launch_keys.h): allocated by the first large batch-leaf launch without a
+  // committee.  `lk` is what kernels take by value; its pointers are filled from the buffers.
   nwc::LaunchKeys lk{};
+  Buf<nwc::u32> lk_keys{bufs, Account::AutoCache, Trimmable};
+  Buf<nwc::u32> lk_flags{bufs, Account::AutoCache, Trimmable};
+  Buf<int32_t> lk_slots{bufs, Account::AutoCache, Trimmable};
+  Buf<nwc::ge_p3> lk_bases{bufs, Account::AutoCache, Trimmable};
+  Buf<uint32_t> lk_state{bufs, Account::AutoCache, Trimmable};
+  Buf<nwc::ge_niels_pad> lk_comb{bufs, Account::AutoCache, Trimmable};
   bool lk_alloc = false;
   bool lk_censused = false;           // the first launch-key launch has measured its keys' demand
-  uint32_t* lk_demand = nullptr;      // host-mapped demand word (lk.host_demand's host side)
+  Buf<uint32_t> lk_demand{bufs, Account::Uncounted, Keep, nwc::buf::Kind::Pinned};   // host-mapped demand word (lk.host_demand's host side)
   // large host calls: pageable inputs through pinned stages on `xfer` (created on first use)
   std::unique_ptr<HostStager> stager;
   std::mutex mu;
 
-  int ensure_pinned(size_t bytes) {
-    if (bytes <= pinned_cap) return 0;
-    if (pinned) { (void)hipHostFree(pinned); pinned = nullptr; pinned_cap = 0; }
-    // coherent: the latency kernel's verdict bytes reach the host while it polls them
-    HIP_TRY(hipHostMalloc(&pinned, bytes, hipHostMallocCoherent));
-    void* dp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dp, pinned, 0));
-    pinned_dev = static_cast<uint8_t*>(dp);
-    pinned_cap = bytes;
-    return 0;
-  }
-  int ensure_arena(size_t bytes) {
-    if (bytes <= arena_cap) return 0;
-    if (arena) { (void)hipFree(arena); arena = nullptr; arena_cap = 0; }
-    size_t cap = bytes + bytes / 4 + (1 << 20);
-    HIP_TRY(hipMalloc(&arena, cap));
-    arena_cap = cap;
-    return 0;
-  }
+  int ensure_pinned(size_t bytes) { HIP_TRY(pinned.ensure(bytes)); return 0; }
+  int ensure_arena(size_t bytes) { HIP_TRY(arena.ensure(bytes, bytes / 4 + (1 << 20))); return 0; }
 };
 
 // slots of the per-device torsion memo of uncached keys (power of two)
@@ -331,8 +347,8 @@ int init_device(DevCtx& d) {
   bpc = 0;
   HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&bpc, reinterpret_cast<const void*>(nwc::k_verify_comb), 256, 0));
   d.comb_blocks_per_cu = bpc > 0 ? bpc : 1;
-  HIP_TRY(hipMalloc(&d.uc_count, sizeof(uint32_t)));
-  HIP_TRY(hipMalloc(&d.fb_count, sizeof(uint32_t)));
+  HIP_TRY(d.uc_count.alloc(sizeof(uint32_t)));
+  HIP_TRY(d.fb_count.alloc(sizeof(uint32_t)));
   HIP_TRY(hipStreamSynchronize(d.stream));
   return 0;
 }
@@ -341,35 +357,34 @@ int init_device(DevCtx& d) {
 // nwc_init: a worker process that only digests batches holds none of them (worker/src/worker.rs:
 // 182-188 -- workers and a primary share the host's GPUs).  Built on d.stream and waited for once,
 // so launches on any stream after it see them.  Caller holds d.mu and has set the device.
-int ensure_verify_tables(DevCtx& d) {
-  if (d.tables_ready) return 0;
-  HIP_TRY(hipMalloc(&d.comb_base, nwc::BaseComb::per * sizeof(nwc::ge_niels_pad)));
+int build_verify_tables(DevCtx& d) {
+  HIP_TRY(d.comb_base.alloc(nwc::BaseComb::per * sizeof(nwc::ge_niels_pad)));
   hipLaunchKernelGGL(nwc::k_build_comb<nwc::BaseComb>, dim3((unsigned)((nwc::BaseComb::per + 255) / 256)), dim3(256), 0, d.stream,
-                     (const nwc::u32*)nullptr, 1u, d.comb_base);
+                     (const nwc::u32*)nullptr, 1u, d.comb_base.get());
   HIP_TRY(hipGetLastError());
   if (settings().comb16) {
     // radix-2^22 basepoint comb (3.2 GB): the committee comb kernel and the cold kernel's s B
-    HIP_TRY(hipMalloc(&d.comb16, nwc::COMB16_TOTAL * sizeof(nwc::ge_niels_pad)));
-    HIP_TRY(hipMalloc(&d.comb16_bases, nwc::COMB16_WINDOWS * sizeof(nwc::ge_p3)));
-    hipLaunchKernelGGL(nwc::k_bcomb_bases, dim3(1), dim3(64), 0, d.stream, d.comb16_bases);
+    HIP_TRY(d.comb16.alloc(nwc::COMB16_TOTAL * sizeof(nwc::ge_niels_pad)));
+    HIP_TRY(d.comb16_bases.alloc(nwc::COMB16_WINDOWS * sizeof(nwc::ge_p3)));
+    hipLaunchKernelGGL(nwc::k_bcomb_bases, dim3(1), dim3(64), 0, d.stream, d.comb16_bases.get());
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(nwc::k_build_comb16, dim3((unsigned)((nwc::COMB16_TOTAL + 255) / 256)), dim3(256), 0, d.stream,
-                       d.comb16, (const nwc::ge_p3*)d.comb16_bases);
+                       d.comb16.get(), (const nwc::ge_p3*)d.comb16_bases);
     HIP_TRY(hipGetLastError());
   }
-  HIP_TRY(hipMalloc(&d.base_table, 2 * 129 * sizeof(nwc::ge_niels)));
-  hipLaunchKernelGGL(nwc::k_build_base_table, dim3(5), dim3(64), 0, d.stream, d.base_table);
+  HIP_TRY(d.base_table.alloc(2 * 129 * sizeof(nwc::ge_niels)));
+  hipLaunchKernelGGL(nwc::k_build_base_table, dim3(5), dim3(64), 0, d.stream, d.base_table.get());
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMalloc(&d.base24, 2 * (size_t)nwc::B24_ENTRIES * sizeof(nwc::ge_niels_pad)));
-  HIP_TRY(hipMalloc(&d.base24_points, 2 * sizeof(nwc::ge_p3)));
-  hipLaunchKernelGGL(nwc::k_base_pow2, dim3(1), dim3(64), 0, d.stream, d.base24_points);
+  HIP_TRY(d.base24.alloc(2 * (size_t)nwc::B24_ENTRIES * sizeof(nwc::ge_niels_pad)));
+  HIP_TRY(d.base24_points.alloc(2 * sizeof(nwc::ge_p3)));
+  hipLaunchKernelGGL(nwc::k_base_pow2, dim3(1), dim3(64), 0, d.stream, d.base24_points.get());
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(nwc::k_build_base_table24, dim3((unsigned)((2 * (size_t)nwc::B24_ENTRIES + 255) / 256)), dim3(256), 0,
-                     d.stream, d.base24, (const nwc::ge_p3*)d.base24_points);
+                     d.stream, d.base24.get(), (const nwc::ge_p3*)d.base24_points);
   HIP_TRY(hipGetLastError());
   // torsion memo: 64K keys (2.3 MB), all slots empty
-  HIP_TRY(hipMalloc(&d.km_keys, 32 * (size_t)NWC_MEMO_SLOTS));
-  HIP_TRY(hipMalloc(&d.km_flag, 4 * (size_t)NWC_MEMO_SLOTS));
+  HIP_TRY(d.km_keys.alloc(32 * (size_t)NWC_MEMO_SLOTS));
+  HIP_TRY(d.km_flag.alloc(4 * (size_t)NWC_MEMO_SLOTS));
   HIP_TRY(hipMemsetAsync(d.km_flag, 0xFF, 4 * (size_t)NWC_MEMO_SLOTS, d.stream));
   // auto key cache: the first AUTO_INIT_KEYS keys' arrays (~330 MB), their slot table and the key
   // comb builder's scratch are allocated here, so the call that first fills the cache only
@@ -378,15 +393,29 @@ int ensure_verify_tables(DevCtx& d) {
     if (int rc = auto_grow(d, std::min<uint32_t>(acap, 16u))) return rc;
     d.ak_slot_cap = 64;
     while (d.ak_slot_cap < 8 * std::min<uint32_t>(acap, 16u)) d.ak_slot_cap <<= 1;
-    HIP_TRY(hipMalloc(&d.ak_slots, 4 * (size_t)d.ak_slot_cap));
+    HIP_TRY(d.ak_slots.alloc(4 * (size_t)d.ak_slot_cap));
     if (!d.kb_bases) {
       d.kb_cap = 64 * (size_t)nwc::KeyComb::windows;
-      HIP_TRY(hipMalloc(&d.kb_bases, d.kb_cap * sizeof(nwc::ge_p3)));
+      HIP_TRY(d.kb_bases.alloc(d.kb_cap * sizeof(nwc::ge_p3)));
     }
   }
   HIP_TRY(hipStreamSynchronize(d.stream));
-  d.tables_ready = true;
   return 0;
+}
+int ensure_verify_tables(DevCtx& d) {
+  if (d.tables_ready) return 0;
+  const int rc = build_verify_tables(d);
+  d.tables_ready = rc == 0;
+  if (rc == 0) return 0;
+  // A failed build holds nothing (out of memory on a GPU shared with other processes is the
+  // expected failure): the builders queued on d.stream are drained, and the next verifying call
+  // starts again from an empty context.
+  (void)hipStreamSynchronize(d.stream);
+  (void)release_each({&d.comb_base, &d.comb16, &d.comb16_bases, &d.base_table, &d.base24, &d.base24_points, &d.km_keys,
+                      &d.km_flag, &d.ak_keys, &d.ak_flags, &d.ak_tables, &d.ak_comb, &d.ak_slots, &d.kb_bases});
+  d.ak_cap = d.ak_slot_cap = 0;
+  d.kb_cap = 0;
+  return rc;
 }
 
 DevCtx* ctx(int i) {
@@ -406,13 +435,12 @@ int build_key_combs(DevCtx& d, const nwc::u32* keys, uint32_t m, nwc::ge_niels_p
   const size_t need = (size_t)m * nwc::KeyComb::windows;
   if (need > d.kb_cap) {
     // stream-ordered: the old bases are freed behind the launches that read them
-    if (d.kb_bases) HIP_TRY(hipFreeAsync(d.kb_bases, d.stream));
-    d.kb_bases = nullptr;
     d.kb_cap = 0;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d.kb_bases), need * sizeof(nwc::ge_p3), d.stream));
+    HIP_TRY(d.kb_bases.release_async(d.stream));
+    HIP_TRY(d.kb_bases.alloc_async(need * sizeof(nwc::ge_p3), d.stream));
     d.kb_cap = need;
   }
-  hipLaunchKernelGGL(nwc::k_comb_key_bases<nwc::KeyComb>, dim3((m + 63) / 64), dim3(64), 0, d.stream, keys, m, d.kb_bases);
+  hipLaunchKernelGGL(nwc::k_comb_key_bases<nwc::KeyComb>, dim3((m + 63) / 64), dim3(64), 0, d.stream, keys, m, d.kb_bases.get());
   HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(nwc::k_build_comb_from_bases<nwc::KeyComb>, dim3((unsigned)(d.cus * 8)), dim3(256), 0, d.stream,
                      (const nwc::ge_p3*)d.kb_bases, 0u, m, (const uint32_t*)nullptr, out);
@@ -427,28 +455,23 @@ constexpr uint32_t AUTO_INIT_KEYS = 16;   // auto-cache capacity allocated at nw
 // the stream's pool (hipMallocAsync), what is built is copied over, and the old arrays are freed
 // behind every launch already queued -- the host never waits.  Caller holds d.mu.
 int auto_grow(DevCtx& d, uint32_t ncap) {
-  nwc::u32 *keys = nullptr, *flags = nullptr;
-  nwc::ge_niels* tables = nullptr;
-  nwc::ge_niels_pad* comb = nullptr;
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&keys), 32 * (size_t)ncap, d.stream));
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&flags), 4 * (size_t)ncap, d.stream));
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&tables), (size_t)ncap * 129 * sizeof(nwc::ge_niels), d.stream));
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&comb), (size_t)ncap * nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad),
-                         d.stream));
-  const size_t n0 = d.ak_n;
-  if (n0) {
-    HIP_TRY(hipMemcpyAsync(keys, d.ak_keys, 32 * n0, hipMemcpyDeviceToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(flags, d.ak_flags, 4 * n0, hipMemcpyDeviceToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(tables, d.ak_tables, n0 * 129 * sizeof(nwc::ge_niels), hipMemcpyDeviceToDevice, d.stream));
-    HIP_TRY(hipMemcpyAsync(comb, d.ak_comb, n0 * nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad), hipMemcpyDeviceToDevice,
-                           d.stream));
+  RawBuf* const held[4] = {&d.ak_keys, &d.ak_flags, &d.ak_tables, &d.ak_comb};
+  const size_t per_key[4] = {32, 4, 129 * sizeof(nwc::ge_niels), nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad)};
+  RawBuf fresh[4];
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < 4 && e == hipSuccess; ++i) e = fresh[i].alloc_async(per_key[i] * ncap, d.stream);
+  for (int i = 0; i < 4 && e == hipSuccess && d.ak_n; ++i)
+    e = hipMemcpyAsync(fresh[i].raw(), held[i]->raw(), per_key[i] * d.ak_n, hipMemcpyDeviceToDevice, d.stream);
+  if (e != hipSuccess) {   // the cache keeps its arrays; the new ones go back to the pool
+    for (RawBuf& b : fresh) (void)b.release_async(d.stream);
+    return set_err(NWC_ERR_DEVICE, "growing the auto key cache to %u keys: %s", ncap, hipGetErrorString(e));
   }
-  if (d.ak_keys) HIP_TRY(hipFreeAsync(d.ak_keys, d.stream));
-  if (d.ak_flags) HIP_TRY(hipFreeAsync(d.ak_flags, d.stream));
-  if (d.ak_tables) HIP_TRY(hipFreeAsync(d.ak_tables, d.stream));
-  if (d.ak_comb) HIP_TRY(hipFreeAsync(d.ak_comb, d.stream));
-  d.ak_keys = keys; d.ak_flags = flags; d.ak_tables = tables; d.ak_comb = comb;
+  for (int i = 0; i < 4; ++i) {   // the old arrays are freed behind the copies
+    if (hipError_t f = held[i]->release_async(d.stream); e == hipSuccess) e = f;
+    (void)held[i]->adopt(std::move(fresh[i]));
+  }
   d.ak_cap = ncap;
+  HIP_TRY(e);
   return 0;
 }
 
@@ -514,9 +537,9 @@ int auto_insert(DevCtx& d, const uint8_t* pks, uint64_t n) {
   std::vector<int32_t> table;
   const uint32_t slots = build_slots(next.keys, n1, table);
   if (slots > d.ak_slot_cap) {
-    if (d.ak_slots) HIP_TRY(hipFreeAsync(d.ak_slots, d.stream));   // after every launch that reads it
-    d.ak_slots = nullptr;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&d.ak_slots), 4 * (size_t)slots, d.stream));
+    d.ak_slot_cap = 0;
+    HIP_TRY(d.ak_slots.release_async(d.stream));   // after every launch that reads it
+    HIP_TRY(d.ak_slots.alloc_async(4 * (size_t)slots, d.stream));
     d.ak_slot_cap = slots;
   }
   d.ak_pend_keys = std::move(add);
@@ -553,45 +576,34 @@ int auto_insert(DevCtx& d, const uint8_t* pks, uint64_t n) {
 // for the resident grid, not for n.
 // bytes of the per-launch lists: fb_list, uc_list, ts_uniq (4 B per entry) and the torsion hash set
 size_t list_bytes(uint64_t cap, uint64_t slots) { return 12 * (size_t)cap + 8 * (size_t)slots; }
-void free_lists(DevCtx& d) {
-  for (void* p : {(void*)d.fb_list, (void*)d.uc_list, (void*)d.ts_slots, (void*)d.ts_flag, (void*)d.ts_uniq})
-    if (p) (void)hipFree(p);
-  d.fb_list = nullptr;
-  d.uc_list = nullptr;
-  d.ts_slots = nullptr;
-  d.ts_flag = nullptr;
-  d.ts_uniq = nullptr;
+int free_lists(DevCtx& d) {
   d.fb_cap = 0;
   d.ts_slot_count = 0;
+  HIP_TRY(release_each({&d.fb_list, &d.uc_list, &d.ts_slots, &d.ts_flag, &d.ts_uniq}));
+  return 0;
 }
 
 int ensure_scratch(DevCtx& d, size_t bytes, uint64_t n) {
   const uint64_t want = n + n / 2 + 4096;
   const bool shrink = !d.hold_lists && d.fb_cap > 4 * want && list_bytes(d.fb_cap, d.ts_slot_count) > settings().verify_keep_bytes;
-  if (bytes <= d.scratch_cap && n <= d.fb_cap && !shrink) return 0;
+  if (d.scratch.fits(bytes) && n <= d.fb_cap && !shrink) return 0;
   HIP_TRY(hipEventSynchronize(d.scratch_free));
-  if (bytes > d.scratch_cap) {
-    if (d.scratch) HIP_TRY(hipFree(d.scratch));
-    d.scratch = nullptr;
-    d.scratch_cap = 0;
-    HIP_TRY(hipMalloc(&d.scratch, bytes));
-    d.scratch_cap = bytes;
-  }
+  HIP_TRY(d.scratch.ensure(bytes));
   if (shrink || n > d.fb_cap) {
-    free_lists(d);
+    if (int rc = free_lists(d)) return rc;
     const size_t c = want;
-    HIP_TRY(hipMalloc(&d.fb_list, 4 * c));
-    HIP_TRY(hipMalloc(&d.uc_list, 4 * c));
+    HIP_TRY(d.fb_list.alloc(4 * c));
+    HIP_TRY(d.uc_list.alloc(4 * c));
     // the hash set stays at most half full: >= 2 slots per equation
     uint32_t slots = 1024;
     while (slots < 2 * c) slots <<= 1;
-    HIP_TRY(hipMalloc(&d.ts_slots, 4 * (size_t)slots));
-    HIP_TRY(hipMalloc(&d.ts_flag, 4 * (size_t)slots));
-    HIP_TRY(hipMalloc(&d.ts_uniq, 4 * c));
+    HIP_TRY(d.ts_slots.alloc(4 * (size_t)slots));
+    HIP_TRY(d.ts_flag.alloc(4 * (size_t)slots));
+    HIP_TRY(d.ts_uniq.alloc(4 * c));
     d.ts_slot_count = slots;
     d.fb_cap = c;
   }
-  if (!d.ts_nuniq) HIP_TRY(hipMalloc(&d.ts_nuniq, sizeof(uint32_t)));
+  if (!d.ts_nuniq) HIP_TRY(d.ts_nuniq.alloc(sizeof(uint32_t)));
   return 0;
 }
 
@@ -605,18 +617,17 @@ int ensure_events(std::vector<hipEvent_t>& ev, size_t n) {
   return 0;
 }
 
-// Replaces the device buffer p by one of need + headroom bytes, once its users have finished: every
-// launch that uses these buffers records scratch_free after its last kernel, so waiting for it
-// (and for *drain, a stream whose queued work may use p as well; nullptr = none) drains them on
-// any stream.
-int regrow(DevCtx& d, uint8_t*& p, size_t& cap, size_t need, const hipStream_t* drain, size_t headroom) {
+// b grown to need + headroom bytes -- or, with `keep`, replaced by a block of `need` when it holds
+// more than keep bytes and under a quarter is needed (Buf::ensure) -- once its users have
+// finished: every launch that uses these buffers records scratch_free after its last kernel, so
+// waiting for it (and for *drain, a stream whose queued work may use b as well; nullptr = none)
+// drains them on any stream.
+int ensure_idle(DevCtx& d, RawBuf& b, size_t need, const hipStream_t* drain, size_t headroom = 0,
+                size_t keep = nwc::buf::NO_SHRINK) {
+  if (b.fits(need, keep)) return 0;
   HIP_TRY(hipEventSynchronize(d.scratch_free));
   if (drain) HIP_TRY(hipStreamSynchronize(*drain));
-  if (p) HIP_TRY(hipFree(p));
-  p = nullptr;
-  cap = 0;
-  HIP_TRY(hipMalloc(&p, need + headroom));
-  cap = need + headroom;
+  HIP_TRY(b.ensure(need, headroom, keep));
   return 0;
 }
 
@@ -659,24 +670,16 @@ int launch_torsion(DevCtx& d, const uint8_t* pks, uint64_t* out_words, uint64_t 
 // (20 MB per key), which grow as keys ask to join; the set starts empty.  Caller holds d.mu.
 int lk_ensure(DevCtx& d, hipStream_t s) {
   if (d.lk_alloc) return 0;
-  nwc::LaunchKeys& k = d.lk;
-  HIP_TRY(hipMalloc(&k.keys, 32 * (size_t)nwc::LK_MAX_KEYS));
-  HIP_TRY(hipMalloc(&k.flags, 4 * (size_t)nwc::LK_MAX_KEYS));
-  HIP_TRY(hipMalloc(&k.slots, 4 * (size_t)nwc::LK_SLOTS));
-  HIP_TRY(hipMalloc(&k.bases, (size_t)nwc::LK_MAX_KEYS * nwc::KeyComb::windows * sizeof(nwc::ge_p3)));
-  HIP_TRY(hipMalloc(&k.state, 16));
-  if (!d.lk_demand) HIP_TRY(hipHostMalloc(&d.lk_demand, sizeof(uint32_t), hipHostMallocCoherent));
-  {
-    // (again after nwc_trim, which resets the set's struct but keeps this word)
-    void* dp = nullptr;
-    HIP_TRY(hipHostGetDevicePointer(&dp, d.lk_demand, 0));
-    k.host_demand = static_cast<uint32_t*>(dp);
-  }
-  *reinterpret_cast<volatile uint32_t*>(d.lk_demand) = 0;
-  k.comb = nullptr;
-  k.cap = 0;
-  HIP_TRY(hipMemsetAsync(k.slots, 0xFF, 4 * (size_t)nwc::LK_SLOTS, s));
-  HIP_TRY(hipMemsetAsync(k.state, 0, 16, s));
+  HIP_TRY(d.lk_keys.alloc(32 * (size_t)nwc::LK_MAX_KEYS));
+  HIP_TRY(d.lk_flags.alloc(4 * (size_t)nwc::LK_MAX_KEYS));
+  HIP_TRY(d.lk_slots.alloc(4 * (size_t)nwc::LK_SLOTS));
+  HIP_TRY(d.lk_bases.alloc((size_t)nwc::LK_MAX_KEYS * nwc::KeyComb::windows * sizeof(nwc::ge_p3)));
+  HIP_TRY(d.lk_state.alloc(16));
+  if (!d.lk_demand) HIP_TRY(d.lk_demand.alloc(sizeof(uint32_t)));   // (nwc_trim keeps this word)
+  *reinterpret_cast<volatile uint32_t*>(d.lk_demand.get()) = 0;
+  d.lk = nwc::LaunchKeys{d.lk_keys, d.lk_flags, d.lk_slots, nullptr, d.lk_bases, d.lk_state, d.lk_demand.dev(), 0};
+  HIP_TRY(hipMemsetAsync(d.lk.slots, 0xFF, 4 * (size_t)nwc::LK_SLOTS, s));
+  HIP_TRY(hipMemsetAsync(d.lk.state, 0, 16, s));
   d.lk_alloc = true;
   d.lk_censused = false;
   return 0;
@@ -699,18 +702,23 @@ int lk_reserve(DevCtx& d, const uint8_t* pks, uint64_t n, hipStream_t s) {
     HIP_TRY(hipStreamSynchronize(s));
     d.lk_censused = true;
   }
-  const uint32_t demand = *reinterpret_cast<volatile uint32_t*>(d.lk_demand);
+  const uint32_t demand = *reinterpret_cast<volatile uint32_t*>(d.lk_demand.get());
   if (demand <= k.cap) return 0;
   const uint32_t cap = std::min<uint32_t>(nwc::LK_MAX_KEYS, (demand + 7) / 8 * 8);
-  nwc::ge_niels_pad* comb = nullptr;
+  Buf<nwc::ge_niels_pad> comb;
   const size_t per = nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad);
-  HIP_TRY(hipMallocAsync(reinterpret_cast<void**>(&comb), (size_t)cap * per, s));
-  if (k.comb) {
-    HIP_TRY(hipMemcpyAsync(comb, k.comb, (size_t)k.cap * per, hipMemcpyDeviceToDevice, s));
-    HIP_TRY(hipFreeAsync(k.comb, s));
+  HIP_TRY(comb.alloc_async((size_t)cap * per, s));
+  if (d.lk_comb) {
+    if (hipError_t e = hipMemcpyAsync(comb, d.lk_comb, (size_t)k.cap * per, hipMemcpyDeviceToDevice, s)) {
+      (void)comb.release_async(s);
+      HIP_TRY(e);
+    }
   }
-  k.comb = comb;
+  const hipError_t freed = d.lk_comb.release_async(s);   // behind the copy
+  (void)d.lk_comb.adopt(std::move(comb));
+  k.comb = d.lk_comb;
   k.cap = cap;
+  HIP_TRY(freed);
   return 0;
 }
 
@@ -738,21 +746,12 @@ int ensure_stager(DevCtx& d) {
 // once holds at most the keep threshold of them while it verifies by other paths.
 int release_idle_buffers(DevCtx& d, const uint8_t* in_use) {
   const size_t keep = settings().verify_keep_bytes;
-  struct Buf { uint8_t** p; size_t* cap; } bufs[] = {
-      {&d.straus_scratch, &d.straus_cap}, {&d.msm_scratch, &d.msm_cap}, {&d.rs_buf, &d.rs_cap},
-      {&d.pair_buf, &d.pair_cap}, {&d.sign_buf, &d.sign_cap}};
-  auto idle = [&](const Buf& b) { return *b.p && *b.p != in_use && *b.p != d.busy_buf && *b.cap > keep; };
-  bool any = false;
-  for (const Buf& b : bufs) any = any || idle(b);
-  if (!any) return 0;
+  RawBuf* const bufs[] = {&d.straus_scratch, &d.msm_scratch, &d.rs_buf, &d.pair_buf, &d.sign_buf};
+  auto idle = [&](const RawBuf* b) { return b->raw() && b->raw() != in_use && b->raw() != d.busy_buf && b->bytes() > keep; };
+  if (std::none_of(std::begin(bufs), std::end(bufs), idle)) return 0;
   HIP_TRY(hipEventSynchronize(d.scratch_free));
-  for (const Buf& b : bufs) {
-    if (idle(b)) {
-      HIP_TRY(hipFree(*b.p));
-      *b.p = nullptr;
-      *b.cap = 0;
-    }
-  }
+  for (RawBuf* b : bufs)
+    if (idle(b)) HIP_TRY(b->release());
   return 0;
 }
 
@@ -1231,14 +1230,14 @@ int verify_small(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words)
   if (sr.mode != SmallMode::Staged) {
     uint8_t* hb = h + align256(c.need);   // byte verdicts of a zero-copy launch, after the staged inputs
     std::memset(hb, 0, n);
-    auto dev = [&](const void* p) { return p ? d.pinned_dev + ((const uint8_t*)p - d.arena) : nullptr; };
+    auto dev = [&](const void* p) { return p ? d.pinned.dev() + ((const uint8_t*)p - d.arena) : nullptr; };
     VerifyLaunch zc = c.launch(0, n, d.stream);
     zc.msgs = dev(c.dm);
     zc.msg_index = reinterpret_cast<const uint32_t*>(dev(c.dmi));
     zc.pks = dev(c.dp);
     zc.sigs = dev(c.ds);
     zc.flags = fl;
-    zc.vbytes = d.pinned_dev + (hb - h);
+    zc.vbytes = d.pinned.dev() + (hb - h);
     if (int rc = launch_verify(d, zc)) return rc;
     // poll the verdict bytes (bit 7 = written); a launch that never writes them (a device error)
     // falls back to the stream wait after 200 ms, which reports the error
@@ -1300,9 +1299,8 @@ int verify_paired(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_words
   const uint64_t gcap = (uint64_t)d.cus * d.verify_blocks_per_cu * NWC_VERIFY_GRID_MULT;
   if (int rc = ensure_scratch(d, (size_t)gcap * 256 * 2 * nwc::TAB_BYTES_PER_LANE, nwc::plan::longest_chunk(cuts))) return rc;
   const size_t counts_bytes = align256(4 * nch), pair_need = counts_bytes + 4 * n;
-  if (pair_need > d.pair_cap)
-    if (int rc = regrow(d, d.pair_buf, d.pair_cap, pair_need, nullptr, 0)) return rc;
-  uint32_t* const counts = reinterpret_cast<uint32_t*>(d.pair_buf);
+  if (int rc = ensure_idle(d, d.pair_buf, pair_need, nullptr)) return rc;
+  uint32_t* const counts = reinterpret_cast<uint32_t*>(d.pair_buf.get());
   uint32_t* const lists = reinterpret_cast<uint32_t*>(d.pair_buf + counts_bytes);
   struct Hold {
     DevCtx& d;
@@ -1373,8 +1371,7 @@ int verify_chunked(DevCtx& d, const HostCall& c, std::vector<uint64_t>& out_word
   if (ysplit) {
     if (int rc = release_idle_buffers(d, d.sign_buf)) return rc;
     const size_t need_s = 2 * (3 * align256(32 * maxlen) + align256(4 * maxlen));
-    if (need_s > d.sign_cap)
-      if (int rc = regrow(d, d.sign_buf, d.sign_cap, need_s, nullptr, 0)) return rc;
+    if (int rc = ensure_idle(d, d.sign_buf, need_s, nullptr)) return rc;
     Carve cs(d.sign_buf);
     for (auto& r : reg) {
       r.x = cs.take<uint32_t>(32 * maxlen);
@@ -1487,13 +1484,11 @@ int verify_range(int di, const uint8_t* msgs, uint64_t msg_stride, const uint32_
 
 // A per-launch device buffer of the batch entries (MSM, Straus, resolve), grown on demand and
 // shrunk back when it holds more than NWC_VERIFY_KEEP_BYTES and a launch needs under a quarter of
-// it (a primary and workers share the GPU: worker/src/worker.rs:182,227).  Every launch that uses
-// these buffers records scratch_free after its last kernel, so waiting for it (and for s) drains
-// their users on any stream before the buffer is replaced.
-int ensure_buf(DevCtx& d, uint8_t*& p, size_t& cap, size_t need, hipStream_t s) {
-  const bool shrink = cap > settings().verify_keep_bytes && need < cap / 4;
-  if (need <= cap && !shrink) return 0;
-  return regrow(d, p, cap, need, &s, 0);
+// it (a primary and workers share the GPU: worker/src/worker.rs:182,227), after the other idle
+// ones above that threshold have gone.
+int ensure_batch_buf(DevCtx& d, Buf<uint8_t>& b, size_t need, hipStream_t s) {
+  if (int rc = release_idle_buffers(d, b)) return rc;
+  return ensure_idle(d, b, need, &s, 0, settings().verify_keep_bytes);
 }
 
 // The per-launch z_i seed: 32 bytes from the host's CSPRNG (dalek: merlin transcript + thread_rng),
@@ -1506,11 +1501,6 @@ void draw_seed(uint32_t seed[8]) {
   }
   static thread_local std::random_device rd;
   for (int i = 0; i < 8; ++i) seed[i] = rd();
-}
-
-int ensure_straus_scratch(DevCtx& d, size_t bytes, hipStream_t s) {
-  if (int rc = release_idle_buffers(d, d.straus_scratch)) return rc;
-  return ensure_buf(d, d.straus_scratch, d.straus_cap, bytes, s);
 }
 
 // dalek's batch equation over sub-batches (k_verify_straus) + the exact leaves for the failing
@@ -1538,7 +1528,7 @@ int launch_straus(DevCtx& d, const uint8_t* dig, const uint32_t* mi, const uint8
   const uint64_t lanes = std::min<uint64_t>((runs + 255) / 256 * 256, resident);
   const uint64_t maxq = (nvotes + runs - 1) / runs;
   const uint64_t stride = maxq * nwc::STRAUS_VOTE_BYTES;
-  if (int rc = ensure_straus_scratch(d, lanes * stride, s)) return rc;
+  if (int rc = ensure_batch_buf(d, d.straus_scratch, lanes * stride, s)) return rc;
   // the failing sub-batches' leaves: the list-mode leaf kernel's scratch and lists
   const uint64_t lgrid = (uint64_t)d.cus * d.verify_blocks_per_cu;
   if (int rc = ensure_scratch(d, (size_t)lgrid * 256 * 2 * nwc::TAB_BYTES_PER_LANE, nvotes)) return rc;
@@ -1603,10 +1593,9 @@ int launch_msm(DevCtx& d, const uint8_t* dig, const uint32_t* mi, const uint8_t*
   // per-wave points and digits, then the failing groups' vote list (count word, entries)
   const size_t list_off = align256((size_t)grid * nwc::MSM_WAVE_BYTES);
   const size_t need = list_off + 256 + 4 * nvotes;
-  if (int rc = release_idle_buffers(d, d.msm_scratch)) return rc;
-  if (int rc = ensure_buf(d, d.msm_scratch, d.msm_cap, need, s)) return rc;
+  if (int rc = ensure_batch_buf(d, d.msm_scratch, need, s)) return rc;
   if (!d.msm_stats) {
-    HIP_TRY(hipMalloc(&d.msm_stats, 4 * nwc::MSM_ST_WORDS));
+    HIP_TRY(d.msm_stats.alloc(4 * nwc::MSM_ST_WORDS));
     HIP_TRY(hipMemsetAsync(d.msm_stats, 0, 4 * nwc::MSM_ST_WORDS, s));
   }
   uint32_t* const mcount = reinterpret_cast<uint32_t*>(d.msm_scratch + list_off);
@@ -1649,14 +1638,13 @@ int launch_resolve(DevCtx& d, const uint8_t* dig, const uint32_t* mi, uint64_t m
   if (nv == 0) return 0;
   if (nv > 0xFFFFFFFFull || m > 0xFFFFFFFFull) return set_err(NWC_ERR_ARG, "more than 2^32 - 1 votes or certificates");
   const size_t state_off = align256(256 + 4 * (size_t)nv);
-  if (int rc = release_idle_buffers(d, d.rs_buf)) return rc;
-  if (int rc = ensure_buf(d, d.rs_buf, d.rs_cap, state_off + align256(4 * (size_t)m), s)) return rc;
+  if (int rc = ensure_batch_buf(d, d.rs_buf, state_off + align256(4 * (size_t)m), s)) return rc;
   // one lane per failing vote; a lane slot's ladder table lives in the verification scratch
   const uint64_t grid = (uint64_t)d.cus * d.verify_blocks_per_cu;
   if (int rc = ensure_scratch(d, (size_t)grid * 256 * 2 * nwc::TAB_BYTES_PER_LANE, std::min(nv, settings().verify_max_launch)))
     return rc;
   HIP_TRY(hipStreamWaitEvent(s, d.scratch_free, 0));
-  uint32_t* const count = reinterpret_cast<uint32_t*>(d.rs_buf);
+  uint32_t* const count = reinterpret_cast<uint32_t*>(d.rs_buf.get());
   uint32_t* const list = count + 64;
   uint32_t* const state = reinterpret_cast<uint32_t*>(d.rs_buf + state_off);
   HIP_TRY(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
@@ -1884,71 +1872,17 @@ void nwc_shutdown(void) {
   for (auto& d : g_devs) {
     std::lock_guard<std::mutex> dl(d->mu);
     (void)hipSetDevice(d->hip_id);
-    if (d->stream) (void)hipStreamSynchronize(d->stream);
-    if (d->sign_table) (void)hipFree(d->sign_table);
-    if (d->arena) (void)hipFree(d->arena);
-    if (d->scratch) (void)hipFree(d->scratch);
-    if (d->fb_list) (void)hipFree(d->fb_list);
-    if (d->fb_count) (void)hipFree(d->fb_count);
-    if (d->pair_buf) (void)hipFree(d->pair_buf);
-    if (d->sign_buf) (void)hipFree(d->sign_buf);
-    if (d->stamps) (void)hipFree(d->stamps);
-    if (d->cm_keys) (void)hipFree(d->cm_keys);
-    if (d->cm_flags) (void)hipFree(d->cm_flags);
-    if (d->cm_tables) (void)hipFree(d->cm_tables);
-    if (d->cm_slots) (void)hipFree(d->cm_slots);
-    if (d->cm_comb) (void)hipFree(d->cm_comb);
-    if (d->ak_keys) (void)hipFree(d->ak_keys);
-    if (d->ak_flags) (void)hipFree(d->ak_flags);
-    if (d->ak_tables) (void)hipFree(d->ak_tables);
-    if (d->ak_comb) (void)hipFree(d->ak_comb);
-    if (d->ak_slots) (void)hipFree(d->ak_slots);
-    if (d->comb_base) (void)hipFree(d->comb_base);
-    if (d->base_table) (void)hipFree(d->base_table);
-    if (d->base24) (void)hipFree(d->base24);
-    if (d->base24_points) (void)hipFree(d->base24_points);
-    if (d->km_keys) (void)hipFree(d->km_keys);
-    if (d->km_flag) (void)hipFree(d->km_flag);
-    if (d->comb16) (void)hipFree(d->comb16);
-    if (d->comb16_bases) (void)hipFree(d->comb16_bases);
-    if (d->kb_bases) (void)hipFree(d->kb_bases);
-    if (d->straus_scratch) (void)hipFree(d->straus_scratch);
-    if (d->msm_scratch) (void)hipFree(d->msm_scratch);
-    if (d->rs_buf) (void)hipFree(d->rs_buf);
-    if (d->msm_stats) (void)hipFree(d->msm_stats);
-    if (d->lk_demand) (void)hipHostFree(d->lk_demand);
-    if (d->lk_alloc) {
-      (void)hipFree(d->lk.keys);
-      (void)hipFree(d->lk.flags);
-      (void)hipFree(d->lk.slots);
-      (void)hipFree(d->lk.comb);
-      (void)hipFree(d->lk.bases);
-      (void)hipFree(d->lk.state);
-    }
-    if (d->pinned) (void)hipHostFree(d->pinned);
-    if (d->cc_stakes) (void)hipFree(d->cc_stakes);
-    if (d->cc_worker_off) (void)hipFree(d->cc_worker_off);
-    if (d->cc_worker_ids) (void)hipFree(d->cc_worker_ids);
-    if (d->msg_arena) (void)hipFree(d->msg_arena);
-    if (d->uc_list) (void)hipFree(d->uc_list);
-    if (d->uc_count) (void)hipFree(d->uc_count);
-    if (d->ts_slots) (void)hipFree(d->ts_slots);
-    if (d->ts_flag) (void)hipFree(d->ts_flag);
-    if (d->ts_uniq) (void)hipFree(d->ts_uniq);
-    if (d->ts_nuniq) (void)hipFree(d->ts_nuniq);
-    if (d->km_keys) (void)hipFree(d->km_keys);
-    if (d->km_flag) (void)hipFree(d->km_flag);
+    // every stream drained, then every buffer (plain frees, the stream-ordered blocks included),
+    // then the events and streams
+    for (hipStream_t st : {d->stream, d->side, d->xfer})
+      if (st) (void)hipStreamSynchronize(st);
+    (void)d->bufs.release_all();
     if (d->scratch_free) (void)hipEventDestroy(d->scratch_free);
-    if (d->base_table) (void)hipFree(d->base_table);
-    if (d->base24) (void)hipFree(d->base24);
-    if (d->base24_points) (void)hipFree(d->base24_points);
-    if (d->side) (void)hipStreamSynchronize(d->side);
     if (d->ev_fork) (void)hipEventDestroy(d->ev_fork);
     if (d->ev_join) (void)hipEventDestroy(d->ev_join);
     if (d->ev_msg) (void)hipEventDestroy(d->ev_msg);
     if (d->ev_count) (void)hipEventDestroy(d->ev_count);
     if (d->side) (void)hipStreamDestroy(d->side);
-    if (d->xfer) (void)hipStreamSynchronize(d->xfer);
     if (d->stager) d->stager->release();
     d->stager.reset();
     for (hipEvent_t e : d->ev_chunk) (void)hipEventDestroy(e);
@@ -2120,41 +2054,31 @@ static int set_committee_locked(const uint8_t* pks, size_t n) {
       HIP_TRY(hipMemsetAsync(d.lk.state, 0, 16, d.stream));
       d.lk_censused = false;
     }
-    if (d.cm_keys) HIP_TRY(hipFree(d.cm_keys));
-    if (d.cm_flags) HIP_TRY(hipFree(d.cm_flags));
-    if (d.cm_tables) HIP_TRY(hipFree(d.cm_tables));
-    if (d.cm_slots) HIP_TRY(hipFree(d.cm_slots));
-    if (d.cm_comb) HIP_TRY(hipFree(d.cm_comb));
-    d.cm_keys = nullptr; d.cm_flags = nullptr; d.cm_tables = nullptr; d.cm_slots = nullptr; d.cm_comb = nullptr;
-    // stake / worker tables are indexed like the cache: a new cache invalidates them
-    // (nwc_set_committee_config sets them again right after)
-    if (d.cc_stakes) HIP_TRY(hipFree(d.cc_stakes));
-    if (d.cc_worker_off) HIP_TRY(hipFree(d.cc_worker_off));
-    if (d.cc_worker_ids) HIP_TRY(hipFree(d.cc_worker_ids));
-    d.cc_stakes = nullptr; d.cc_worker_off = nullptr; d.cc_worker_ids = nullptr; d.cc_n = 0;
-    d.cm_n = 0; d.cm_slot_mask = 0; d.cm_bytes = 0;
+    // the old cache, and the stake / worker tables indexed like it (nwc_set_committee_config sets
+    // those again right after)
+    d.cm_n = 0; d.cm_slot_mask = 0; d.cc_n = 0;
+    HIP_TRY(release_each({&d.cm_keys, &d.cm_flags, &d.cm_tables, &d.cm_slots, &d.cm_comb, &d.cc_stakes, &d.cc_worker_off,
+                          &d.cc_worker_ids}));
     if (n == 0) continue;
-    HIP_TRY(hipMalloc(&d.cm_keys, 32 * n));
-    HIP_TRY(hipMalloc(&d.cm_flags, 4 * n));
-    HIP_TRY(hipMalloc(&d.cm_tables, n * 129 * sizeof(nwc::ge_niels)));
-    HIP_TRY(hipMalloc(&d.cm_slots, 4 * (size_t)slots));
+    HIP_TRY(d.cm_keys.alloc(32 * n));
+    HIP_TRY(d.cm_flags.alloc(4 * n));
+    HIP_TRY(d.cm_tables.alloc(n * 129 * sizeof(nwc::ge_niels)));
+    HIP_TRY(d.cm_slots.alloc(4 * (size_t)slots));
     HIP_TRY(hipMemcpyAsync(d.cm_keys, keys.data(), 32 * n, hipMemcpyHostToDevice, d.stream));
     HIP_TRY(hipMemcpyAsync(d.cm_slots, table.data(), 4 * (size_t)slots, hipMemcpyHostToDevice, d.stream));
     const unsigned grid = (unsigned)((n * 129 + 255) / 256);
-    hipLaunchKernelGGL(nwc::k_build_key_tables, dim3(grid), dim3(256), 0, d.stream, d.cm_keys, (nwc::u32)n,
-                       d.cm_tables, d.cm_flags);
+    hipLaunchKernelGGL(nwc::k_build_key_tables, dim3(grid), dim3(256), 0, d.stream, d.cm_keys.get(), (nwc::u32)n,
+                       d.cm_tables.get(), d.cm_flags.get());
     HIP_TRY(hipGetLastError());
     if (n <= NWC_COMB_MAX_KEYS) {
       // per-key combs for the doubling-free path (radix 2^14: 20 MB per key)
       const size_t entries = n * nwc::COMB_PER_KEY;
-      HIP_TRY(hipMalloc(&d.cm_comb, entries * sizeof(nwc::ge_niels_pad)));
+      HIP_TRY(d.cm_comb.alloc(entries * sizeof(nwc::ge_niels_pad)));
       if (int rc = build_key_combs(d, d.cm_keys, (uint32_t)n, d.cm_comb)) return rc;
     }
     HIP_TRY(hipStreamSynchronize(d.stream));
     d.cm_n = (uint32_t)n;
     d.cm_slot_mask = slots - 1;
-    d.cm_bytes = 36 * n + n * 129 * sizeof(nwc::ge_niels) + 4 * (size_t)slots +
-                 (d.cm_comb ? n * nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad) : 0);
   }
   if (n) {
     std::lock_guard<std::mutex> lk(g_hcm.mu);
@@ -2291,7 +2215,7 @@ int nwc_diag_verify_clock(const void* d_msgs, uint64_t msg_stride, const void* d
     return set_err(NWC_ERR_ARG, "the clock stamp needs a single launch (n <= %llu)", (unsigned long long)settings().verify_max_launch);
   // one stamp slot per wave of the largest grid launch_verify gives k_verify
   const uint64_t nwaves = (uint64_t)d.cus * d.verify_blocks_per_cu * NWC_VERIFY_GRID_MULT * 4;
-  if (!d.stamps) HIP_TRY(hipMalloc(&d.stamps, 32 * nwaves));
+  if (!d.stamps) HIP_TRY(d.stamps.alloc(32 * nwaves));
   HIP_TRY(hipMemsetAsync(d.stamps, 0, 32 * nwaves, s));
   if (int rc = launch_verify(d, {.msgs = (const uint8_t*)d_msgs, .msg_stride = msg_stride, .pks = (const uint8_t*)d_pks,
                                  .sigs = (const uint8_t*)d_sigs, .n = n, .strict = 1, .out_words = (uint64_t*)d_verdict_words,
@@ -2450,15 +2374,11 @@ int nwc_set_committee_config(const uint8_t* pks, const uint64_t* stakes, size_t 
     std::lock_guard<std::mutex> lk(d.mu);
     HIP_TRY(hipSetDevice(d.hip_id));
     HIP_TRY(hipStreamSynchronize(d.stream));
-    if (d.cc_stakes) HIP_TRY(hipFree(d.cc_stakes));
-    if (d.cc_worker_off) HIP_TRY(hipFree(d.cc_worker_off));
-    if (d.cc_worker_ids) HIP_TRY(hipFree(d.cc_worker_ids));
-    d.cc_stakes = nullptr; d.cc_worker_off = nullptr; d.cc_worker_ids = nullptr;
     d.cc_n = 0;
     d.cc_quorum = 2 * total / 3 + 1;   // Committee::quorum_threshold (config/src/lib.rs:168-173)
-    HIP_TRY(hipMalloc(&d.cc_stakes, 8 * (n + 1)));
-    HIP_TRY(hipMalloc(&d.cc_worker_off, 4 * (n + 1)));
-    HIP_TRY(hipMalloc(&d.cc_worker_ids, 4 * (size_t)(nw + 1)));
+    HIP_TRY(d.cc_stakes.alloc(8 * (n + 1)));   // (set_committee_locked released the old tables)
+    HIP_TRY(d.cc_worker_off.alloc(4 * (n + 1)));
+    HIP_TRY(d.cc_worker_ids.alloc(4 * (size_t)(nw + 1)));
     if (n) {
       HIP_TRY(hipMemcpy(d.cc_stakes, stakes, 8 * n, hipMemcpyHostToDevice));
       HIP_TRY(hipMemcpy(d.cc_worker_off, worker_offsets, 4 * (n + 1), hipMemcpyHostToDevice));
@@ -2505,8 +2425,7 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
                       align256(64 * vt) + align256(4 * vt) + align256(4) + align256(4 * m) + align256(16 * m) +
                       align256(4 * m) + align256(8 * ((m + 63) / 64)) + align256(8 * ((vt + 63) / 64)) +
                       (ysplit ? 3 * align256(32 * vt) + align256(4 * vt) + 3 * align256(32 * m) + align256(4 * m) : 0);
-  if (need > d.msg_arena_cap)
-    if (int rc = regrow(d, d.msg_arena, d.msg_arena_cap, need, &s, need / 4 + (1 << 20))) return rc;
+  if (int rc = ensure_idle(d, d.msg_arena, need, &s, need / 4 + (1 << 20))) return rc;
   Carve c(d.msg_arena);
   nwc::MsgArgs a{};   // the whole call's arrays
   a.data = ddata;
@@ -2553,7 +2472,7 @@ static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, s
   }
   if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
   if (4 * nch > (64u << 10)) return set_err(NWC_ERR_ARG, "too many chunks");   // counts below sanitize_range's offsets
-  uint32_t* nv_host = reinterpret_cast<uint32_t*>(d.pinned);   // pinned: the count copies stay asynchronous
+  uint32_t* nv_host = reinterpret_cast<uint32_t*>(d.pinned.get());   // pinned: the count copies stay asynchronous
   if (int rc = ensure_events(d.ev_cnt, nch)) return rc;
   // the leaf stream when chunks overlap: the side stream, which has a hardware queue of its own
   // (GPU_MAX_HW_QUEUES = 4: a stream created later shared the transfer stream's queue, and its
@@ -2952,22 +2871,11 @@ int nwc_memory_info(nwc_memory* out) {
   *out = nwc_memory{};
   {
     std::lock_guard<std::mutex> lk(d.mu);
-    // built by the first call that verifies or signs (ensure_verify_tables); 0 before
-    out->tables = !d.tables_ready ? 0 :
-                  2 * 129 * sizeof(nwc::ge_niels) + 2 * (size_t)nwc::B24_ENTRIES * sizeof(nwc::ge_niels_pad) +
-                  2 * sizeof(nwc::ge_p3) + nwc::BaseComb::per * sizeof(nwc::ge_niels_pad) +
-                  (d.comb16 ? nwc::COMB16_TOTAL * sizeof(nwc::ge_niels_pad) + nwc::COMB16_WINDOWS * sizeof(nwc::ge_p3) : 0) +
-                  36 * (size_t)NWC_MEMO_SLOTS;
-    if (d.sign_table) out->tables += nwc::SIGN_TABLE_BYTES;   // a process that only signs holds this one alone
-    out->committee = d.cm_bytes;
-    out->auto_cache = (size_t)d.ak_cap * (36 + 129 * sizeof(nwc::ge_niels) + nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad)) +
-                      4 * (size_t)d.ak_slot_cap + d.kb_cap * sizeof(nwc::ge_p3) +
-                      (d.lk_alloc ? (size_t)nwc::LK_MAX_KEYS * (36 + nwc::KeyComb::windows * sizeof(nwc::ge_p3)) +
-                                        (size_t)d.lk.cap * nwc::COMB_PER_KEY * sizeof(nwc::ge_niels_pad) +
-                                        4 * (size_t)nwc::LK_SLOTS + 16
-                                  : 0);
-    out->scratch = d.scratch_cap + d.straus_cap + d.msm_cap + d.rs_cap + d.arena_cap + d.msg_arena_cap + 12 * d.fb_cap + d.pair_cap + d.sign_cap +
-                   8 * (size_t)d.ts_slot_count;
+    // tables: built by the first call that verifies (ensure_verify_tables) or signs (sign_table); 0 before
+    out->tables = d.bufs.bytes(Account::Tables);
+    out->committee = d.bufs.bytes(Account::Committee);
+    out->auto_cache = d.bufs.bytes(Account::AutoCache);
+    out->scratch = d.bufs.bytes(Account::Scratch);
   }
   out->digesters = digester_device_bytes(d.hip_id);
   size_t fr = 0, tot = 0;
@@ -2987,32 +2895,15 @@ int nwc_trim(void) {
   HIP_TRY(hipSetDevice(d.hip_id));
   // every stream: nwc_dev_* launches on callers' streams read these buffers too
   HIP_TRY(hipDeviceSynchronize());
-  if (d.scratch) HIP_TRY(hipFree(d.scratch));
-  if (d.straus_scratch) HIP_TRY(hipFree(d.straus_scratch));
-  if (d.msm_scratch) HIP_TRY(hipFree(d.msm_scratch));
-  d.msm_scratch = nullptr; d.msm_cap = 0;
-  if (d.rs_buf) HIP_TRY(hipFree(d.rs_buf));
-  d.rs_buf = nullptr; d.rs_cap = 0;
-  if (d.pair_buf) HIP_TRY(hipFree(d.pair_buf));
-  d.pair_buf = nullptr; d.pair_cap = 0;
-  if (d.sign_buf) HIP_TRY(hipFree(d.sign_buf));
-  d.sign_buf = nullptr; d.sign_cap = 0;
-  if (d.arena) HIP_TRY(hipFree(d.arena));
-  if (d.msg_arena) HIP_TRY(hipFree(d.msg_arena));
-  d.scratch = nullptr; d.scratch_cap = 0;
-  d.straus_scratch = nullptr; d.straus_cap = 0;
-  d.arena = nullptr; d.arena_cap = 0;
-  d.msg_arena = nullptr; d.msg_arena_cap = 0;
-  // the per-launch lists (fallback, uncached, torsion hash set) and the launch-key set (2.6 GB of
-  // combs): the next launch that needs them allocates them again, the launch keys empty
-  free_lists(d);
-  if (d.lk_alloc) {
-    for (void* p : {(void*)d.lk.keys, (void*)d.lk.flags, (void*)d.lk.slots, (void*)d.lk.comb, (void*)d.lk.bases,
-                    (void*)d.lk.state})
-      HIP_TRY(hipFree(p));
-    d.lk = nwc::LaunchKeys{};
-    d.lk_alloc = false;
-  }
+  // the table slots, arenas and batch buffers, the per-launch lists (fallback, uncached, torsion
+  // hash set) and the launch-key set (2.6 GB of combs): the next launch that needs them allocates
+  // them again, the launch keys empty
+  const hipError_t freed = d.bufs.release_trimmable();
+  d.fb_cap = 0;
+  d.ts_slot_count = 0;
+  d.lk = nwc::LaunchKeys{};
+  d.lk_alloc = false;
+  HIP_TRY(freed);
   return 0;
 }
 

@@ -32,16 +32,14 @@ void wipe(volatile uint8_t* p, size_t n) {
 // The signer's basepoint table (60 KB), built by the device's first signer.  Caller holds d.mu.
 int ensure_sign_table(DevCtx& d) {
   if (d.sign_table) return 0;
-  nwc::ge_niels* t = nullptr;
-  HIP_TRY(hipMalloc(&t, nwc::SIGN_TABLE_BYTES));
-  hipLaunchKernelGGL(nwc::k_build_sign_table, dim3(nwc::SIGN_TABLE_ENTRIES / 64), dim3(64), 0, d.stream, t);
+  HIP_TRY(d.sign_table.alloc(nwc::SIGN_TABLE_BYTES));
+  hipLaunchKernelGGL(nwc::k_build_sign_table, dim3(nwc::SIGN_TABLE_ENTRIES / 64), dim3(64), 0, d.stream, d.sign_table.get());
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
   if (e != hipSuccess) {
-    (void)hipFree(t);
+    (void)d.sign_table.release();
     return set_err(NWC_ERR_DEVICE, "building the signer table failed: %s", hipGetErrorString(e));
   }
-  d.sign_table = t;
   return 0;
 }
 
@@ -56,8 +54,8 @@ int expand_key(DevCtx& d, const uint8_t* seed, const uint8_t* pub, nwc::SignKey*
   if (pub) std::memcpy(h + 32, pub, 32);
   else std::memset(h + 32, 0, 32);
   std::memset(h + 64, 0, 36);
-  hipLaunchKernelGGL(nwc::k_sign_expand, dim3(1), dim3(64), 0, d.stream, (const uint8_t*)d.pinned_dev, pub ? 1 : 0,
-                     (const nwc::ge_niels*)d.sign_table, key, d.pinned_dev + 64, reinterpret_cast<uint32_t*>(d.pinned_dev + 96));
+  hipLaunchKernelGGL(nwc::k_sign_expand, dim3(1), dim3(64), 0, d.stream, (const uint8_t*)d.pinned.dev(), pub ? 1 : 0,
+                     (const nwc::ge_niels*)d.sign_table, key, d.pinned.dev() + 64, reinterpret_cast<uint32_t*>(d.pinned.dev() + 96));
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(d.stream);
   wipe(h, 32);
@@ -192,7 +190,7 @@ int nwc_signer_sign_many(void* signer, const uint8_t* msgs32, size_t n, uint8_t*
     uint8_t* h = d.pinned;
     std::memcpy(h, msgs32 + 32 * lo, 32 * c);
     std::memset(h + fo, 0, c);
-    if (int rc = launch_sign(d, sg.key, d.pinned_dev, 32, c, d.pinned_dev + so, d.pinned_dev + fo, wide, d.stream)) return rc;
+    if (int rc = launch_sign(d, sg.key, d.pinned.dev(), 32, c, d.pinned.dev() + so, d.pinned.dev() + fo, wide, d.stream)) return rc;
     // poll the "written" bytes (stored after the signature's words and a system fence); a launch
     // that never writes them (a device error) falls back to the stream wait after 200 ms
     const bool poll = spin && c <= NWC_WIDE_MAX;

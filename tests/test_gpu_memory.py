@@ -264,6 +264,38 @@ print("after one verify", mem2, flush=True)
     print(r.stdout)
 
 
+def test_trim_walk_in_a_fresh_process(tmp_path):
+    """A fresh process without a committee (tests/memory_walk_helper.py): a strict launch of 4,096
+    equations, a batch-leaf launch of 65,536 (the launch-key threshold: the set and its combs are
+    allocated), the Straus, MSM and dalek entries over 64 certificates of 8 votes -- votes of 16 keys,
+    every 7th corrupted -- then nwc_trim and the five calls again.  Every verdict equals the
+    construction (asserted in the helper); the trim leaves no scratch, the tables as they were and
+    the auto cache at its value from before the launch keys; the second round holds after each call
+    what the first held."""
+    import json
+    import subprocess
+    import sys
+    from tests.conftest import ROOT
+    out = tmp_path / "walk.json"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "memory_walk_helper.py"), str(out), ROOT],
+                       capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
+    steps = {s["step"]: s for s in json.load(open(out))["steps"]}
+    for s in steps.values():
+        print(s)
+    assert steps["start"]["tables"] == 0 and steps["inputs"]["tables"] > (2 << 30) and steps["inputs"]["scratch"] == 0
+    assert steps["1:leaf"]["auto_cache"] > steps["1:strict"]["auto_cache"]   # the launch keys and their combs
+    assert steps["1:dalek"]["scratch"] > 0
+    trim = steps["trim"]
+    assert trim["scratch"] == 0, trim
+    assert trim["tables"] == steps["1:dalek"]["tables"] == steps["inputs"]["tables"], (trim, steps["1:dalek"])
+    assert trim["auto_cache"] == steps["1:strict"]["auto_cache"], (trim, steps["1:strict"])
+    for call in ("strict", "leaf", "straus", "msm", "dalek"):
+        a, b = steps["1:" + call], steps["2:" + call]
+        assert (a["scratch"], a["auto_cache"], a["tables"]) == (b["scratch"], b["auto_cache"], b["tables"]), (a, b)
+        assert a["committee"] == b["committee"] == 0
+
+
 def test_batch_entry_buffers_above_keep_are_released():
     """The Straus tables (~3.8 GB at config-3 size) and the MSM groups' scratch (~1.3 GB) stay only
     while their entry runs: the next launch of another path frees them (NWC_VERIFY_KEEP_BYTES), so
