@@ -26,6 +26,7 @@
 #include <stdint.h>
 #include "fe25519.h"
 #include "ge25519.h"
+#include "ge_u25519.h"
 #include "sc25519.h"
 #include "sha512.h"
 #include "lattice.h"
@@ -435,6 +436,16 @@ constexpr int TAB_U4_PER_ENTRY = 8;
 
 // f (limbs |f_i| < 2^26.5 even / 2^25.5 odd: sums of two tight elements) + 2p, floor-carried to
 // limbs in [0, 2^26) / [0, 2^25) (limb 1 < 2^25 + 2), packed into two uint4.
+__device__ __forceinline__ void pack_limbs(const u32 h[10], uint4& lo, uint4& hi) {
+  lo.x = h[0] | (h[1] << 26);
+  lo.y = (h[1] >> 6) | (h[2] << 20);
+  lo.z = (h[2] >> 12) | (h[3] << 14);
+  lo.w = (h[3] >> 18) | (h[4] << 7);
+  hi.x = (h[4] >> 25) | (h[5] << 1) | (h[6] << 26);
+  hi.y = (h[6] >> 6) | (h[7] << 20);
+  hi.z = (h[7] >> 12) | (h[8] << 13);
+  hi.w = (h[8] >> 19) | (h[9] << 7);
+}
 __device__ __forceinline__ void fe_pack(const fe& f, uint4& lo, uint4& hi) {
   u32 h[10];
   i32 c = 0;
@@ -448,14 +459,22 @@ __device__ __forceinline__ void fe_pack(const fe& f, uint4& lo, uint4& hi) {
   h[0] += 19u * (u32)c;                // c <= 3: h[0] < 2^26 + 57
   h[1] += h[0] >> 26;
   h[0] &= (1u << 26) - 1u;
-  lo.x = h[0] | (h[1] << 26);
-  lo.y = (h[1] >> 6) | (h[2] << 20);
-  lo.z = (h[2] >> 12) | (h[3] << 14);
-  lo.w = (h[3] >> 18) | (h[4] << 7);
-  hi.x = (h[4] >> 25) | (h[5] << 1) | (h[6] << 26);
-  hi.y = (h[6] >> 6) | (h[7] << 20);
-  hi.z = (h[7] >> 12) | (h[8] << 13);
-  hi.w = (h[8] >> 19) | (h[9] << 7);
+  pack_limbs(h, lo, hi);
+}
+// The non-negative field's entry (fe_u25519.h): any f <= 3 T, no bias; the same carries and layout.
+__device__ __forceinline__ void feu_pack(const feu& f, uint4& lo, uint4& hi) {
+  u32 h[10];
+  u32 c = 0;
+  _Pragma("unroll") for (int i = 0; i < 10; ++i) {
+    const int w = (i & 1) ? 25 : 26;
+    const u32 v = f.v[i] + c;
+    c = v >> w;
+    h[i] = v & ((1u << w) - 1u);
+  }
+  h[0] += 19u * c;                     // c <= 3: h[0] < 2^26 + 57
+  h[1] += h[0] >> 26;
+  h[0] &= (1u << 26) - 1u;
+  pack_limbs(h, lo, hi);
 }
 // Unpacked limbs are in [0, 2^26) / [0, 2^25 + 2): within the multiplier's loose input bound
 // (including the 19x on the right operand).
@@ -474,6 +493,11 @@ __device__ __forceinline__ fe fe_unpack(const uint4& lo, const uint4& hi) {
   r.v[9] = (i32)(hi.w >> 7);
   return r;
 }
+// the same limbs as a (tight) element of the non-negative field
+__device__ __forceinline__ feu feu_unpack(const uint4& lo, const uint4& hi) {
+  const fe s = fe_unpack(lo, hi);
+  feu r; _Pragma("unroll") for (int i = 0; i < 10; ++i) r.v[i] = (u32)s.v[i]; return r;
+}
 constexpr size_t TAB_BYTES_PER_LANE = TAB_ENTRIES * TAB_U4_PER_ENTRY * 16;   // 1440 (1152 packed)
 
 struct LaneTable {
@@ -483,6 +507,15 @@ struct LaneTable {
     _Pragma("unroll") for (int k = 0; k < 4; ++k) {
       uint4 lo, hi;
       fe_pack(co[k], lo, hi);
+      p[e * 8 + 2 * k] = lo;
+      p[e * 8 + 2 * k + 1] = hi;
+    }
+  }
+  __device__ __forceinline__ void store(int e, const geu_cached& c) const {
+    const feu* co = &c.YpX;
+    _Pragma("unroll") for (int k = 0; k < 4; ++k) {
+      uint4 lo, hi;
+      feu_pack(co[k], lo, hi);
       p[e * 8 + 2 * k] = lo;
       p[e * 8 + 2 * k + 1] = hi;
     }
@@ -851,9 +884,82 @@ __device__ __forceinline__ void base_adds(ge_p1p1& t, int nb, i32 d0, i32 d1, ui
   }
 }
 
-__device__ __forceinline__ ge_p2 half_scalarmult(const LaneTable& ta, const LaneTable& tr, Digits16 cd, Digits16 dd,
-                                                 BaseDigits bd, const ge_niels_pad* T24,
-                                                 uint4* stage, int W) {
+// ---- the uncached half-size ladder on the non-negative field (fe_u25519.h, ge_u25519.h) ------
+// The per-lane tables hold (Y+X, Y-X, 2Z, 2dT), packed as above; every unpacked coordinate is tight.
+__device__ __forceinline__ feu lt_load_feu(const LaneTable& tab, int e, int k) {
+  return feu_unpack(tab.p[e * 8 + 2 * k], tab.p[e * 8 + 2 * k + 1]);
+}
+// tab[j] = j * P for j = 0..8 (tab[0] = identity).  P: X, T <= 2 T, Y, Z tight (geu_decompress, negated or not).
+__device__ __forceinline__ void build_table_u(const LaneTable& tab, const geu_p3& P) {
+  const geu_cached p1 = geu_p3_to_cached(P);   // YpX, YmX 3 T, Z2 2 T, T2d tight: right operands below
+  geu_cached id;
+  id.YpX = feu_one(); id.YmX = feu_one(); id.Z2 = feu_add(feu_one(), feu_one()); id.T2d = feu_zero();
+  tab.store(0, id);
+  tab.store(1, p1);
+  geu_p2 p2; p2.X = P.X; p2.Y = P.Y; p2.Z = P.Z;                 // X 2 T, Y, Z tight
+  geu_p3 pj = geu_p1p1_to_p3(geu_p2_dbl(p2));                    // all tight
+  tab.store(2, geu_p3_to_cached(pj));
+#pragma unroll 1
+  for (int j = 3; j < TAB_ENTRIES; ++j) {
+    pj = geu_p1p1_to_p3(geu_add_cached(pj, p1.YpX, p1.YmX, p1.Z2, p1.T2d, false));
+    tab.store(j, geu_p3_to_cached(pj));
+  }
+}
+// The ladder's first entry as a completed point (2X : 2Y : 2Z : 2Z): X 3 T, Y 2 T, Z = T tight.
+__device__ __forceinline__ geu_p1p1 lt_first_u(const LaneTable& tab, int e) {
+  const feu ypx = lt_load_feu(tab, e, 0), ymx = lt_load_feu(tab, e, 1);
+  geu_p1p1 r;
+  r.X = feu_sub<2>(ypx, ymx);
+  r.Y = feu_add(ypx, ymx);
+  r.Z = lt_load_feu(tab, e, 2);
+  r.T = r.Z;
+  return r;
+}
+// t + (neg ? -q : q) for q = tab[e], as add_lt: the entry is read coordinate by coordinate, Y+X and
+// Y-X (swapped for -q, a per-lane address choice) before the extended form is built, 2Z and 2dT after.
+// t: X <= 4 T, Z <= 4 T, T and Y <= 3 T (the output of a doubling or of an addition).
+__device__ __forceinline__ geu_p1p1 add_lt_u(const geu_p1p1& t, const LaneTable& tab, int e, bool neg) {
+  const feu qa = lt_load_feu(tab, e, neg ? 1 : 0);   // tight
+  const feu qb = lt_load_feu(tab, e, neg ? 0 : 1);   // tight
+  const geu_p3 p = geu_p1p1_to_p3(t);                // all tight
+  __builtin_amdgcn_sched_barrier(0);
+  const feu qz = lt_load_feu(tab, e, 2);             // tight
+  const feu qt = lt_load_feu(tab, e, 3);             // tight
+  return geu_add_cached(p, qa, qb, qz, qt, neg);
+}
+// four doublings of t (t in, t out), (X:Y:Z) only; one rolled doubling body
+__device__ __forceinline__ void ladder_dbl4_u(geu_p1p1& t) {
+  geu_p2 p2 = geu_p1p1_to_p2(t);
+#pragma unroll 1
+  for (int j = 0; j < 3; ++j) { t = geu_p2_dbl(p2); p2 = geu_p1p1_to_p2(t); }
+  t = geu_p2_dbl(p2);
+}
+// as base_adds; the T24 entries are signed (fe25519.h) and shared with the other kernels, so they
+// are biased on load: y+x, y-x + 2p (<= 3.01 T), 2dxy + p (<= 1.51 T) -- 30 VOP2 for each of 11 adds
+__device__ __forceinline__ void base_adds_u(geu_p1p1& t, int nb, i32 d0, i32 d1, uint4* stage,
+                                            const ge_niels_pad* T24) {
+  if (nb) {
+    stage_wait();
+#pragma unroll 1
+    for (int side = 0; side < nb; ++side) {
+      const i32 dd_ = side ? d1 : d0;
+      const ge_niels e = stage_read(stage, 0);
+      if (side + 1 < nb) {
+        __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): entry 0 is in VGPRs before the slot is reused
+        stage_fetch(stage, 0, T24 + B24_ENTRIES + (d1 < 0 ? -d1 : d1));
+      }
+      const bool neg = dd_ < 0;
+      const feu qa = feu_from_fe<2>(fe_select(e.ypx, e.ymx, neg));
+      const feu qb = feu_from_fe<2>(fe_select(e.ymx, e.ypx, neg));
+      t = geu_add_niels(geu_p1p1_to_p3(t), qa, qb, feu_from_fe<1>(e.xy2d), neg);
+      if (side + 1 < nb) stage_wait();
+    }
+  }
+}
+
+__device__ __forceinline__ geu_p2 half_scalarmult(const LaneTable& ta, const LaneTable& tr, Digits16 cd, Digits16 dd,
+                                                  BaseDigits bd, const ge_niels_pad* T24,
+                                                  uint4* stage, int W) {
   // Code-size discipline: the window body holds ONE doubling and ONE Niels add (rolled loops) and
   // two cached adds, so the hot loop stays inside the instruction cache.
   i32 da = cd.top, dr = dd.top;   // top digits are >= 0
@@ -863,7 +969,7 @@ __device__ __forceinline__ ge_p2 half_scalarmult(const LaneTable& ta, const Lane
   // scalars
   park16(bd, BD_C, cd);
   park16(bd, BD_D, dd);
-  ge_p1p1 t = ge_cached_to_p1p1(lt_first(ta, da));
+  geu_p1p1 t = lt_first_u(ta, da);
 #pragma unroll 1
   for (int w = W - 1; w >= 0; --w) {
     i32 d0 = 0, d1 = 0;
@@ -871,15 +977,15 @@ __device__ __forceinline__ ge_p2 half_scalarmult(const LaneTable& ta, const Lane
     // after it then never wait on the DMA (vmcnt counts in order)
     const int nb = base_fetch(w, bd, d0, d1, T24, stage);
     if (w != W - 1) {
-      ladder_dbl4(t);
+      ladder_dbl4_u(t);
       da = digit16(bd, BD_C, w, W);
-      t = add_lt(t, ta, da < 0 ? -da : da, da < 0);
+      t = add_lt_u(t, ta, da < 0 ? -da : da, da < 0);
       dr = digit16(bd, BD_D, w, W);
     }
-    t = add_lt(t, tr, dr < 0 ? -dr : dr, dr < 0);
-    base_adds(t, nb, d0, d1, stage, T24);
+    t = add_lt_u(t, tr, dr < 0 ? -dr : dr, dr < 0);
+    base_adds_u(t, nb, d0, d1, stage, T24);
   }
-  return ge_p1p1_to_p2(t);
+  return geu_p1p1_to_p2(t);
 }
 
 // The same ladder over digit strings already parked in LDS (BD_C, BD_D; top digits passed in).
@@ -991,6 +1097,33 @@ __device__ __forceinline__ void prologue(Prologue& p, const u32 mw[8], const u32
   challenge(rw, aw, mw, p.kw);
 }
 
+// The same prologue on the non-negative field, for the uncached half-size equation.  One noinline
+// decompression body (I-cache), called only by the half-size k_verify kernels, so their launch
+// bounds set its register budget.
+__device__ __noinline__ void decompress_u(geu_p3* out, const u32* a, u32* ycanon, bool* ok) {
+  u32 w[8];
+  _Pragma("unroll") for (int i = 0; i < 8; ++i) w[i] = a[i];
+  geu_decompress(w, *out, ycanon, *ok);
+}
+struct PrologueU {
+  geu_p3 A, R;
+  u32 kw[8], sw[8];
+  bool ok;   // s < l, A and R decode, and (strict) neither is small-order
+};
+__device__ __forceinline__ void prologue_u(PrologueU& p, const u32 mw[8], const u32 aw[8], const u32 sigw[16],
+                                           bool strict) {
+  u32 rw[8];
+  _Pragma("unroll") for (int i = 0; i < 8; ++i) { rw[i] = sigw[i]; p.sw[i] = sigw[8 + i]; }
+  const bool s_ok = sc_lt_l(p.sw);
+  u32 ya[8], yr[8];
+  bool oka, okr;
+  decompress_u(&p.A, aw, ya, &oka);
+  decompress_u(&p.R, rw, yr, &okr);
+  const bool small = strict && (ycanon_is_small_order(ya) || ycanon_is_small_order(yr));
+  p.ok = s_ok && oka && okr && !small;
+  challenge(rw, aw, mw, p.kw);
+}
+
 // Full-length equation: R' = k(-A) + sB == R.
 __device__ bool verify_full(const u32 mw[8], const u32 aw[8], const u32 sigw[16], bool strict, const ge_niels* sB,
                             const LaneTable& tab) {
@@ -1072,8 +1205,8 @@ __device__ __forceinline__ bool verify_half(const u32 mw[8], const u32 aw[8], co
     const bool ident = fe_is_zero(q.X) && fe_is_zero(fe_sub(q.Y, q.Z));
     return ok && ident && h.ok;
   }
-  Prologue p;
-  prologue<1>(p, mw, aw, sigw, strict);
+  PrologueU p;
+  prologue_u(p, mw, aw, sigw, strict);
   const lat::HalfScalars h = lat::reduce(p.kw);
   const int W = max(wave_windows(h.ok ? h.bits : 0), min(force_w, HALF_WINDOWS_MAX));
   fallback = !h.ok;
@@ -1084,10 +1217,10 @@ __device__ __forceinline__ bool verify_half(const u32 mw[8], const u32 aw[8], co
   }
   const Digits16 cd = recode16(h.c, W), dd = recode16(h.d, W);
   // -c A = |c| * (c < 0 ? A : -A);  -d R = d * (-R)
-  build_table(ta, h.c_neg ? p.A : ge_p3_neg(p.A));
-  build_table(tr, ge_p3_neg(p.R));
-  const ge_p2 q = half_scalarmult(ta, tr, cd, dd, bd, T24, stage, W);
-  const bool ident = fe_is_zero(q.X) && fe_is_zero(fe_sub(q.Y, q.Z));
+  build_table_u(ta, geu_p3_neg(p.A, !h.c_neg));
+  build_table_u(tr, geu_p3_neg(p.R, true));
+  const geu_p2 q = half_scalarmult(ta, tr, cd, dd, bd, T24, stage, W);   // X, Y, Z tight
+  const bool ident = feu_is_zero(q.X) && feu_is_zero(feu_sub<2>(q.Y, q.Z));
   return p.ok && ident && h.ok;
 }
 

@@ -9,6 +9,9 @@ per multiply.  Here every column is exactly one chain of v_mad_i64_i32 whose fir
 column bias (an SGPR pair), and the chains of the 10 columns are issued round-robin so that
 consecutive instructions are independent (dependency distance 10 for fe_mul, >= 5 for fe_sq).
 
+Also generates narwhal_amd/csrc/feu_asm.h, the products of the non-negative field (fe_u25519.h):
+the same columns as v_mad_u64_u32 chains, each seeded with the previous column's carry (emit_u).
+
 Column layout (radix 2^25.5, see fe25519.h): column k collects f_i g_j with i + j = k (mod 10);
 a wrapped product (i + j >= 10) carries 19, a product of two odd limbs carries 2.
 """
@@ -98,7 +101,69 @@ FE_DEV void %s(%s, i64 h[10]) {
 """ % (doc, name, "const fe& f, const fe& g" if "mul" in name else "const fe& f", "\n  ".join(decl), body, outs, ins)
 
 
+OUT_U = os.path.join(os.path.dirname(HERE), "narwhal_amd", "csrc", "feu_asm.h")
+U_MUL = {"f": 1, "g": 1, "f2": 2, "f4": 4, "g19": 19, "f19": 19, "f38": 38}
+
+
+def emit_u(name, cols, doc):
+    """The unsigned, carry-seeded product (fe_u25519.h): column k is one v_mad_u64_u32 chain whose
+    first addend is the carry of column k - 1; a 64-bit shift and a mask end it.  One asm statement
+    per column (inline asm cannot name the low half of a 64-bit operand, which the mask needs), so
+    the whole product is one serial chain -- the layout tools/microbench/mad_chain.hip measured.
+    The same text builds for the host and for the bound shadow through the FEU_* macros."""
+    mul = "mul" in name
+    names = []
+    for c in cols:
+        for a, b in c:
+            for x in (a, b):
+                if x not in names:
+                    names.append(x)
+    body = []
+    for n in names:
+        kind, i = n.split("_")
+        src = ("g" if kind.startswith("g") else "f") + ".v[%s]" % i
+        body.append("const FEU_OP %s = FEU_PREP(%du, %s);" % (n, U_MUL[kind], src))
+    body.append("feu r; FEU_ACC h;")
+    for k, col in enumerate(cols):
+        ops = []
+        for a, b in col:
+            for x in (a, b):
+                if x not in ops:
+                    ops.append(x)
+        idx = {n: 1 + i for i, n in enumerate(ops)}
+        lines = []
+        for t, (a, b) in enumerate(col):
+            src2 = "0" if (k == 0 and t == 0) else "%0"
+            lines.append("v_mad_u64_u32 %%0, vcc, %%%d, %%%d, %s" % (idx[a], idx[b], src2))
+        w = 25 if k & 1 else 26
+        body.append("#if FEU_USE_ASM")
+        body.append('asm("%s" : %s : %s : "vcc");' % ("\\n\\t".join(lines), '"=&v"(h)' if k == 0 else '"+v"(h)',
+                                                      ", ".join('"v"(%s)' % n for n in ops)))
+        body.append("#else")
+        if k == 0:
+            body.append("h = 0;")
+        body.append(" ".join("FEU_MA(h, %s, %s);" % (a, b) for a, b in col))
+        body.append("#endif")
+        body.append("FEU_COL_END(h); r.v[%d] = (u32)h & %du; h >>= %d;" % (k, (1 << w) - 1, w))
+    # the carry out of column 9 re-enters limb 0 with weight 19 (it can pass 2^32: a 64-bit step),
+    # and what limb 0 then carries stays on limb 1 as slack
+    body.append("h = (FEU_ACC)r.v[0] + h * 19u; FEU_COL_END(h);")
+    body.append("r.v[0] = (u32)h & %du; r.v[1] += (u32)(h >> 26);" % ((1 << 26) - 1))
+    body.append("return r;")
+    return "// %s\nFEU_FN feu %s(%s) {\n  %s\n}\n" % (doc, name, "const feu& f, const feu& g" if mul else "const feu& f",
+                                                    "\n  ".join(body))
+
+
 def main():
+    usrc = ["// Generated by tools/gen_fe_asm.py -- do not edit.  Included by fe_u25519.h inside namespace nwc,",
+            "// after feu / u32 / u64 and the FEU_* macros (not a standalone header; no include guard, so a",
+            "// host test can include it a second time, in a namespace of its own, with the macros of its",
+            "// 128-bit bound shadow).",
+            emit_u("feu_mul", mul_terms(), "f * g, carried (100 v_mad_u64_u32)"),
+            emit_u("feu_sq", sq_terms(False), "f^2, carried (55 v_mad_u64_u32)"),
+            emit_u("feu_sq2", sq_terms(True), "2 f^2, carried (55 v_mad_u64_u32)"), ""]
+    open(OUT_U, "w").write("\n".join(usrc))
+    print("wrote", OUT_U)
     src = ["// Generated by tools/gen_fe_asm.py -- do not edit.  Included by fe25519.h after the",
            "// definitions of fe / i32 / i64 / FE_DEV (not a standalone header).", "#pragma once",
            "namespace nwc {",
