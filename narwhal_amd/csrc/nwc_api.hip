@@ -21,7 +21,6 @@
 #include <mutex>
 #include <random>
 #include <string>
-#include <functional>
 #include <thread>
 #include <unordered_set>
 #include <vector>
@@ -32,6 +31,7 @@
 #include "kernels.hip"
 #include "launch_keys.h"
 #include "messages.h"
+#include "msg_plan.h"
 #include "verify_plan.h"
 
 namespace {
@@ -288,7 +288,7 @@ struct HostCommittee {
 };
 HostCommittee g_hcm;
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using nwc::plan::align256;
 
 struct Carve {
   uint8_t* base;
@@ -2389,474 +2389,10 @@ int nwc_set_committee_config(const uint8_t* pks, const uint64_t* stakes, size_t 
   return 0;
 }
 
-// Device part of nwc_sanitize_messages: messages in HBM (ddata 4-byte aligned with >= 16 bytes
-// of readable padding, doff device u64[m+1] relative to ddata, `total` bytes), parsed as the
-// chunks cuts[k] .. cuts[k+1] (whole messages).  `chunk_ready(k)`, when given, returns once chunk
-// k's bytes are on their way and stream s waits for them (the host path's copies);
-// `chunk_queued(k)` tells without waiting whether they are, and chunk k's parse is then queued
-// before the host waits for chunk k - 1's count.  The chunks share one vote-slot counter, so the
-// votes of the chunks parsed so far are contiguous; after each parse the host reads the count and
-// launches those votes' leaves on the side stream beside the next chunk's parse, and the rest
-// after the last chunk.  (Measured and removed in round 6: leaves behind the parses on one stream,
-// leaves in whole comb rounds, per-launch list passes, each parse queued only after the previous
-// count -- profiles/r05/wire_host.md, ab_wire_modes.txt, ab_wire_defer_lists.txt.)
-// The strict equations (headers' and votes' own signatures) of all chunks but the last run while
-// the last one crosses PCIe; the header digests and the final codes run once over all m messages.
-static int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, size_t m, uint64_t total,
-                        const std::vector<size_t>& cuts, uint64_t gc_round, const uint8_t* vote_target, int32_t* dcodes,
-                        uint8_t* ddigests, uint32_t* drec, hipStream_t s,
-                        const std::function<int(size_t)>& chunk_ready = nullptr,
-                        const std::function<bool(size_t)>& chunk_queued = nullptr) {
-  if (int rc = ensure_verify_tables(d)) return rc;
-  const size_t nch = cuts.size() - 1;
-  // a vote list is allocated only when wholly inside its message (>= 72 B per vote)
-  const uint64_t vt = total / 72 + 1 + (nch > 1 ? 64 * nch : 0);   // + the 64-slot alignment of each chunk
-  if (vt > 0xFFFFFFFFull) return set_err(NWC_ERR_ARG, "too many vote slots in one call");
-  // the leaf launches of a chunked call on the committee-cache comb path only list their uncached
-  // equations (LV_DEFER_LIST); the list's half-size, fallback and torsion passes run once, after
-  // the leaves queued before the first strict launch (which reuses the list), instead of ~8 small
-  // launches per chunk on the leaf stream.  Their sign tests are deferred too (SignRecs,
-  // k_verify_comb_y / k_comb_sign): a chunk's ~1 vote per lane would otherwise pay a whole
-  // inversion per vote.  NWC_SIGN_DEFER=0: k_verify_comb per chunk (A/B).
-  const bool chunked = nch > 1;
-  const bool defer = chunked && deferrable_list(d);
-  const bool ysplit = defer && settings().sign_defer;
-  const size_t need = align256(total + 128 * (m + 2)) + align256(32 * m) * 3 + align256(64 * m) + align256(32 * vt) +
-                      align256(64 * vt) + align256(4 * vt) + align256(4) + align256(4 * m) + align256(16 * m) +
-                      align256(4 * m) + align256(8 * ((m + 63) / 64)) + align256(8 * ((vt + 63) / 64)) +
-                      (ysplit ? 3 * align256(32 * vt) + align256(4 * vt) + 3 * align256(32 * m) + align256(4 * m) : 0);
-  if (int rc = ensure_idle(d, d.msg_arena, need, &s, need / 4 + (1 << 20))) return rc;
-  Carve c(d.msg_arena);
-  nwc::MsgArgs a{};   // the whole call's arrays
-  a.data = ddata;
-  a.offsets = doff;
-  a.m = m;
-  a.gc_round = gc_round;
-  a.hashbuf = c.take<uint8_t>(total + 128 * (m + 2));
-  a.eq_msg = c.take<uint8_t>(32 * m);
-  a.eq_pk = c.take<uint8_t>(32 * m);
-  a.eq_sig = c.take<uint8_t>(64 * m);
-  a.cdig = c.take<uint8_t>(32 * m);
-  a.v_pk = c.take<uint8_t>(32 * vt);
-  a.v_sig = c.take<uint8_t>(64 * vt);
-  a.v_msg = c.take<uint32_t>(4 * vt);
-  a.v_total = c.take<uint32_t>(4);
-  a.v_cap = vt;
-  a.hmatch = c.take<uint32_t>(4 * m);
-  a.rec = drec ? drec : c.take<uint32_t>(16 * m);
-  a.rec_n = c.take<uint32_t>(4 * m);
-  uint64_t* sbits = c.take<uint64_t>(8 * ((m + 63) / 64));
-  uint64_t* lbits = c.take<uint64_t>(8 * ((vt + 63) / 64));
-  nwc::SignRecs sr{};   // vote v's record at index v
-  if (ysplit) {
-    sr.x = c.take<uint32_t>(32 * vt);
-    sr.z = c.take<uint32_t>(32 * vt);
-    sr.p = c.take<uint32_t>(32 * vt);
-    sr.meta = c.take<uint32_t>(4 * vt);
-    HIP_TRY(hipMemsetAsync(lbits, 0, 8 * ((vt + 63) / 64), s));   // the sign and list passes OR into it
-  }
-  nwc::SignRecs srs{};   // the strict equations' records (message i at index i)
-  if (ysplit) {
-    srs.x = c.take<uint32_t>(32 * m);
-    srs.z = c.take<uint32_t>(32 * m);
-    srs.p = c.take<uint32_t>(32 * m);
-    srs.meta = c.take<uint32_t>(4 * m);
-    HIP_TRY(hipMemsetAsync(sbits, 0, 8 * ((m + 63) / 64), s));
-  }
-  a.digests = ddigests;
-  if (vote_target) {
-    a.target.enabled = 1;
-    std::memcpy(a.target.id, vote_target, 32);
-    std::memcpy(&a.target.round, vote_target + 32, 8);
-    std::memcpy(a.target.origin, vote_target + 40, 32);
-  }
-  if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
-  if (4 * nch > (64u << 10)) return set_err(NWC_ERR_ARG, "too many chunks");   // counts below sanitize_range's offsets
-  uint32_t* nv_host = reinterpret_cast<uint32_t*>(d.pinned.get());   // pinned: the count copies stay asynchronous
-  if (int rc = ensure_events(d.ev_cnt, nch)) return rc;
-  // the leaf stream when chunks overlap: the side stream, which has a hardware queue of its own
-  // (GPU_MAX_HW_QUEUES = 4: a stream created later shared the transfer stream's queue, and its
-  // leaves waited behind the markers of the in-flight copies, profiles/r05/wire_host.md)
-  const hipStream_t ls = chunked ? d.side : s;
-  struct HoldLists {
-    DevCtx& d;
-    ~HoldLists() { d.hold_lists = false; }
-  } hold{d};
-  if (defer) {
-    if (int rc = ensure_scratch(d, 0, vt)) return rc;
-    d.hold_lists = true;
-    HIP_TRY(hipStreamWaitEvent(ls, d.scratch_free, 0));
-    HIP_TRY(hipMemsetAsync(d.uc_count, 0, sizeof(uint32_t), ls));
-  }
-  bool pending = false;   // deferred leaf launches whose list passes have not been queued
-  HIP_TRY(hipMemsetAsync(a.v_total, 0, 4, s));
-  HIP_TRY(hipMemsetAsync(a.v_msg, 0, 4 * vt, s));
-  const nwc::Committee cm = committee_of(d);
-  const nwc::CommitteeCfg cc{d.cc_stakes, d.cc_worker_off, d.cc_worker_ids, d.cc_quorum, d.cc_n};
-  const size_t first_lds = 4 * (size_t)std::max<uint32_t>(1, std::min<uint32_t>(d.cc_n, nwc::MSG_MAX_COMMITTEE));
-  // NWC_HOST_TIMING: host-side stamps of the steps (which call waits on what)
-  const bool timing = settings().host_timing;
-  const auto tm0 = std::chrono::steady_clock::now();
-  std::vector<std::pair<const char*, double>> marks;
-  auto mark = [&](const char* what) {
-    if (timing) marks.emplace_back(what, std::chrono::duration<double>(std::chrono::steady_clock::now() - tm0).count() * 1e3);
-  };
-  uint64_t launched = 0;   // votes [0, launched) have their leaf launch queued
-  bool list_dirty = false;   // a strict launch on ls has reused the uncached list since its reset
-  // ysplit: votes [owed_lo, owed_hi) have had their leaves but not their sign tests yet; those run
-  // in the first blocks of the next chunk's leaf launch (k_verify_comb_y_sign), so their
-  // latency-bound chain overlaps its comb sums, or alone before a list pass needs their words
-  uint64_t owed_lo = 0, owed_hi = 0;
-  auto leaves = [&](uint64_t upto, bool deferred) -> int {
-    if (upto <= launched) return 0;
-    if (deferred && list_dirty) {
-      HIP_TRY(hipMemsetAsync(d.uc_count, 0, sizeof(uint32_t), ls));
-      list_dirty = false;
-    }
-    const uint64_t v0 = launched;
-    const bool y = deferred && ysplit;
-    const nwc::SignPass sp{sr, owed_lo, owed_hi - owed_lo, lbits, comb_sign_blocks(d, owed_hi - owed_lo)};
-    const nwc::SignRecs srl = sign_recs_at(sr, (int64_t)v0);
-    if (int rc = launch_verify(d, {.msgs = a.cdig, .msg_index = a.v_msg + v0, .pks = a.v_pk + 32 * v0, .sigs = a.v_sig + 64 * v0,
-                                   .n = upto - v0, .out_words = lbits + v0 / 64, .stream = ls,
-                                   .flags = deferred ? LV_DEFER_LIST : 0, .list_base = v0, .sign_recs = y ? &srl : nullptr,
-                                   .sign_pass = y ? &sp : nullptr}))
-      return rc;
-    if (y) {
-      owed_lo = v0;
-      owed_hi = upto;
-    }
-    pending = pending || deferred;
-    launched = upto;
-    mark("leaves queued");
-    return 0;
-  };
-  // the list passes of the deferred leaves so far (they OR the uncached votes' bits into the words
-  // the comb or sign kernels wrote), after the sign tests still owed
-  auto finish = [&]() -> int {
-    if (owed_hi > owed_lo) {
-      if (int rc = launch_comb_sign(d, sr, owed_lo, owed_hi - owed_lo, lbits, ls)) return rc;
-      owed_lo = owed_hi;
-    }
-    if (!pending) return 0;
-    pending = false;
-    return finish_deferred_list(d, a.cdig, a.v_msg, 0, a.v_pk, a.v_sig, launched, 0, lbits, ls);
-  };
-  // the strict equations (headers' and votes' own signatures) of messages [c0, c1) on the leaf
-  // stream, after the list passes (the strict launch reuses the list)
-  // With the cache holding exactly the configured committee (g_cm_is_config) and the sign tests
-  // deferred, strict equations [c0, c1) go on the parse stream as k_verify_comb_y without a list
-  // (an uncached key is a non-member: UnknownAuthority decides first) and their sign pass, off the
-  // leaf stream, which then carries only the leaves and their list passes.
-  bool strict_y = false;   // set below once the cuts are known to be aligned
-  auto strict = [&](size_t c0, size_t c1) -> int {
-    if (c1 <= c0) return 0;
-    if (strict_y) {
-      const uint64_t n = c1 - c0;
-      const nwc::VerifyArgs va{a.eq_msg + 32 * c0, nullptr, 1, a.eq_pk + 32 * c0, a.eq_sig + 64 * c0, sbits + c0 / 64,
-                               n, 1, d.base_table, d.base24, d.scratch, d.fb_list, d.fb_count, 0u, cm};
-      const nwc::CombArgs ca{nullptr, nullptr, d.comb_base, d.comb16, nullptr, 0};
-      const unsigned gy = (unsigned)std::min<uint64_t>((n + 255) / 256, 60000);
-      hipLaunchKernelGGL(nwc::k_verify_comb_y, dim3(gy), dim3(256), 0, s, va, ca, sign_recs_at(srs, (int64_t)c0));
-      HIP_TRY(hipGetLastError());
-      return launch_comb_sign(d, srs, c0, n, sbits, s);
-    }
-    if (int rc = finish()) return rc;
-    list_dirty = true;
-    return launch_verify(d, {.msgs = a.eq_msg + 32 * c0, .msg_stride = 1, .pks = a.eq_pk + 32 * c0, .sigs = a.eq_sig + 64 * c0,
-                             .n = c1 - c0, .strict = 1, .out_words = sbits + c0 / 64, .stream = ls});
-  };
-  // The strict equations of the first chunks go in one launch after chunk strict_at's leaves,
-  // early, where the leaf stream has slack to absorb its ~0.17 ms (a latency-bound launch); the
-  // rest at the end (every cut is a multiple of 64 messages, sanitize_range: each strict launch
-  // owns its verdict words).  (A strict launch per chunk, each after a list pass, measured 20 %
-  // slower; at chunk nch - 3 instead of nch / 3, within noise: profiles/r06/wire_sign/.)
-  bool aligned = true;
-  for (size_t k = 1; k < nch; ++k) aligned = aligned && (cuts[k] & 63) == 0;
-  const size_t strict_at = aligned && nch >= 3 ? nch / 3 : (nch >= 2 ? nch - 2 : 0);   // its iteration k
-  strict_y = ysplit && aligned && g_cm_is_config.load() && settings().strict_y;
-  size_t strict_done = 0;   // messages [0, strict_done) have their strict launch queued
-  uint64_t nv = 0;
-  size_t queued = 0;   // chunks whose parse is queued
-  auto queue_parse = [&]() -> int {
-    const size_t k = queued++;
-    if (chunk_ready)
-      if (int rc = chunk_ready(k)) return rc;
-    mark("chunk ready");
-    const size_t c0 = cuts[k];
-    nwc::MsgArgs ak = a;
-    ak.offsets = doff + c0;
-    ak.m = cuts[k + 1] - c0;
-    ak.hashbuf = a.hashbuf + 128 * c0;   // the message's slot: aligned data offset + 128 x (call-wide index)
-    ak.eq_msg = a.eq_msg + 32 * c0;
-    ak.eq_pk = a.eq_pk + 32 * c0;
-    ak.eq_sig = a.eq_sig + 64 * c0;
-    ak.cdig = a.cdig + 32 * c0;
-    ak.msg_base = (uint32_t)c0;
-    ak.hmatch = a.hmatch + c0;
-    ak.rec = a.rec + 4 * c0;
-    ak.rec_n = a.rec_n + c0;
-    ak.digests = ddigests ? ddigests + 32 * c0 : nullptr;
-    hipLaunchKernelGGL(nwc::k_parse_messages, dim3((unsigned)ak.m), dim3(64), first_lds, s, ak, cm, cc);
-    HIP_TRY(hipGetLastError());
-    if (nch > 1) {
-      // the next chunk's votes from a 64-slot boundary: every leaf launch starts on its own
-      // verdict word (the skipped slots repeat the last vote; their leaves are never read)
-      hipLaunchKernelGGL(nwc::k_align_slots, dim3(1), dim3(64), 0, s, a.v_total, (uint32_t)vt, a.v_pk, a.v_sig,
-                         a.v_msg);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(nv_host + k, a.v_total, 4, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipEventRecord(d.ev_cnt[k], s));
-    mark("parse queued");
-    return 0;
-  };
-  if (int rc = queue_parse()) return rc;
-  for (size_t k = 0; k < nch; ++k) {
-    // the next chunk's parse goes in before this chunk's count is awaited when its copy is already
-    // queued (no wait on the copier): it then follows this parse on the GPU without a host round
-    // trip in between
-    if (queued < nch && (!chunk_queued || chunk_queued(queued)))
-      if (int rc = queue_parse()) return rc;
-    if (!chunked) continue;
-    // the votes parsed so far on the leaf stream; the next chunk's copy goes on in the copier
-    // thread meanwhile, and its parse runs beside these leaves
-    HIP_TRY(hipEventSynchronize(d.ev_cnt[k]));
-    nv = std::min<uint64_t>(nv_host[k], vt);
-    mark("count");
-    HIP_TRY(hipStreamWaitEvent(ls, d.ev_cnt[k], 0));
-    // (the last leaf launch then holds only the last chunk's votes)
-    if (k + 1 < nch)
-      if (int rc = leaves(nv, defer)) return rc;
-    if (k == strict_at) {
-      if (int rc = strict(0, cuts[k + 1])) return rc;
-      strict_done = cuts[k + 1];
-    }
-    if (queued == k + 1 && queued < nch)
-      if (int rc = queue_parse()) return rc;
-  }
-  if (chunked) {
-    // the Header::digest checks once, beside the last leaves (latency-bound: ~0.2 ms for any
-    // number of messages, so not per chunk)
-    hipLaunchKernelGGL(nwc::k_header_digests, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, a);
-    HIP_TRY(hipGetLastError());
-    if (ysplit) {
-      // the last chunk's leaves deferred as well (a fresh list: the strict launch reused it),
-      // their sign tests, then the list passes and the remaining strict equations
-      if (int rc = leaves(nv, true)) return rc;
-      if (int rc = strict(strict_done, m)) return rc;
-      if (int rc = finish()) return rc;   // (strict_y: the strict launches left the leaf stream's passes)
-    } else {
-      if (int rc = strict(strict_done, m)) return rc;
-      if (int rc = leaves(nv, false)) return rc;
-    }
-    HIP_TRY(hipEventRecord(d.ev_msg, ls));
-    HIP_TRY(hipStreamWaitEvent(s, d.ev_msg, 0));
-  } else {
-    // one chunk: the strict launch (it needs no count) queued before the host waits for the
-    // count, the Header::digest checks beside the leaves on the side stream
-    if (int rc = launch_verify(d, {.msgs = a.eq_msg, .msg_stride = 1, .pks = a.eq_pk, .sigs = a.eq_sig, .n = m, .strict = 1,
-                                   .out_words = sbits, .stream = s}))
-      return rc;
-    HIP_TRY(hipEventRecord(d.ev_fork, s));
-    HIP_TRY(hipStreamWaitEvent(d.side, d.ev_fork, 0));
-    hipLaunchKernelGGL(nwc::k_header_digests, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, d.side, a);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(d.ev_msg, d.side));
-    HIP_TRY(hipEventSynchronize(d.ev_cnt[0]));
-    if (int rc = leaves(std::min<uint64_t>(nv_host[0], vt), false)) return rc;
-    HIP_TRY(hipStreamWaitEvent(s, d.ev_msg, 0));
-  }
-  hipLaunchKernelGGL(nwc::k_finalize_messages, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, a.rec,
-                     a.rec_n, a.hmatch, sbits, lbits, (uint64_t)m, dcodes);
-  HIP_TRY(hipGetLastError());
-  mark("final queued");
-  if (timing && nch > 1) {
-    std::string line;
-    for (const auto& mk : marks) line += std::string(" ") + mk.first + "@" + std::to_string(mk.second).substr(0, 5);
-    std::fprintf(stderr, "nwc sanitize steps:%s\n", line.c_str());
-  }
-  return 0;
-}
-
-static int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t m, uint64_t gc_round,
-                          const uint8_t* vote_target, int32_t* codes, uint8_t* digests32, uint8_t* kinds);
-
-int nwc_sanitize_messages(const uint8_t* data, const uint64_t* offsets, size_t m, uint64_t gc_round,
-                          const uint8_t* vote_target, int32_t* codes, uint8_t* digests32, uint8_t* kinds) {
-  if (int rc = require_init()) return rc;
-  if (m == 0) return 0;
-  if (!data || !offsets || !codes) return set_err(NWC_ERR_ARG, "null buffer");
-  for (size_t i = 0; i < m; ++i)
-    if (offsets[i + 1] < offsets[i]) return set_err(NWC_ERR_ARG, "offsets not monotone at %zu", i);
-  // messages are independent: contiguous ranges per device, one host thread each
-  return shard(m, [&](int di, uint64_t lo, uint64_t hi) -> int {
-    return sanitize_range(di, data, offsets + lo, hi - lo, gc_round, vote_target, codes + lo,
-                          digests32 ? digests32 + 32 * lo : nullptr, kinds ? kinds + lo : nullptr);
-  });
-}
-
-static int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t m, uint64_t gc_round,
-                          const uint8_t* vote_target, int32_t* codes, uint8_t* digests32, uint8_t* kinds) {
-  if (m == 0) return 0;
-  const uint64_t base = offsets[0], total = offsets[m] - base;
-  DevCtx& d = *ctx(di);
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.hip_id));
-  if (int rc = ensure_verify_tables(d)) return rc;
-  if (!d.cc_stakes) return set_err(NWC_ERR_NOT_INIT, "nwc_set_committee_config has not been called");
-  // staging area (the arena): message bytes, offsets, codes, records, digests
-  const size_t need = align256(total + 16) + align256(8 * (m + 1)) + align256(4 * m) + align256(16 * m) +
-                      align256(32 * m);
-  if (int rc = d.ensure_arena(need)) return rc;
-  Carve c(d.arena);
-  uint8_t* ddata = c.take<uint8_t>(total + 16);
-  uint64_t* doff = c.take<uint64_t>(8 * (m + 1));
-  int32_t* dcodes = c.take<int32_t>(4 * m);
-  uint32_t* drec = c.take<uint32_t>(16 * m);
-  uint8_t* ddig = digests32 ? c.take<uint8_t>(32 * m) : nullptr;
-  std::vector<uint64_t> hoff(m + 1);
-  for (size_t i = 0; i <= m; ++i) hoff[i] = offsets[i] - base;
-  const bool staged = total >= ((size_t)4 << 20);
-  // Large batches (config 3 from the wire: 10 KB per certificate) go through the pinned stages on
-  // the transfer stream in chunks of ~NWC_MSG_CHUNK bytes cut on message boundaries; chunk k is
-  // parsed and verified while chunk k + 1 crosses PCIe.  The chunks share the message offsets
-  // (uploaded first, relative to ddata) and the message arena (sanitize_dev, run per chunk in
-  // stream order).
-  const uint64_t msg_chunk = settings().msg_chunk;   // 0 = one copy, then one pass (A/B)
-  // chunk sizes: from 16 MB doubling up to msg_chunk, and never more than half of what remains
-  // (>= 8 MB, so the last one is <= 16 MB): the first parse starts after a short copy, and the
-  // work left when the last copy lands (that chunk's parse, leaves and strict equations, the
-  // codes) is small; each leaf launch costs >= ~0.18 ms whatever its size, so not smaller
-  std::vector<size_t> cuts{0};
-  const uint64_t lo = std::min<uint64_t>((uint64_t)8 << 20, msg_chunk);
-  if (staged && msg_chunk && total >= 4 * lo) {
-    uint64_t at = 0, next = std::min<uint64_t>(msg_chunk, 2 * lo);
-    while (total - at > 2 * lo) {
-      const uint64_t want = std::max(lo, std::min(next, (total - at) / 2));
-      // every cut on a multiple of 64 messages: each chunk's strict launch owns its verdict words
-      size_t cm = (size_t)(std::lower_bound(hoff.begin(), hoff.end(), at + want) - hoff.begin()) & ~(size_t)63;
-      if (cm <= cuts.back()) cm = cuts.back() + 64;
-      if (cm >= m) break;
-      cuts.push_back(cm);
-      at = hoff[cm];
-      next = std::min<uint64_t>(msg_chunk, 2 * next);
-    }
-    // the last cut on a multiple of 64 messages (the strict launches' verdict words)
-    while (cuts.size() > 1 && (cuts.back() & 63)) {
-      const size_t c = cuts.back() & ~(size_t)63;
-      cuts.pop_back();
-      if (c > cuts.back()) cuts.push_back(c);
-    }
-  }
-  cuts.push_back(m);
-  const size_t nch = cuts.size() - 1;
-  HIP_TRY(hipMemsetAsync(ddata + total, 0, 16, d.stream));
-  // the offsets through pinned memory when they fit beside the chunk counts (a pageable source
-  // makes the copy wait for the host)
-  const size_t hoff_at = 64u << 10;
-  if (8 * (m + 1) <= NWC_PINNED_STAGE_MAX - hoff_at) {
-    if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
-    uint8_t* const ph = static_cast<uint8_t*>(d.pinned) + hoff_at;
-    std::memcpy(ph, hoff.data(), 8 * (m + 1));
-    HIP_TRY(hipMemcpyAsync(doff, ph, 8 * (m + 1), hipMemcpyHostToDevice, d.stream));
-  } else {
-    HIP_TRY(hipMemcpyAsync(doff, hoff.data(), 8 * (m + 1), hipMemcpyHostToDevice, d.stream));
-  }
-  if (!staged) {
-    HIP_TRY(hipMemcpyAsync(ddata, data + base, total, hipMemcpyHostToDevice, d.stream));
-    if (int rc = sanitize_dev(d, ddata, doff, m, total, {0, m}, gc_round, vote_target, dcodes, ddig, drec, d.stream))
-      return rc;
-  } else {
-    if (int rc = ensure_stager(d)) return rc;
-    if (int rc = ensure_events(d.ev_chunk, nch)) return rc;
-    // the copies wait for every launch that may still read the arena
-    HIP_TRY(hipEventRecord(d.ev_fork, d.stream));
-    HIP_TRY(hipStreamWaitEvent(d.xfer, d.ev_fork, 0));
-    d.stager->reset();
-    const auto tm0 = std::chrono::steady_clock::now();
-    std::chrono::steady_clock::time_point tm_copied = tm0;
-    // a copy thread fills the stages chunk by chunk and records each chunk's event; this thread
-    // runs chunk k once its event has been recorded (a wait on an unrecorded event would not wait)
-    std::mutex cmu;
-    std::condition_variable ccv;
-    size_t recorded = 0;
-    hipError_t copy_err = hipSuccess;
-    std::thread copier([&] {
-      hipError_t e = hipSetDevice(d.hip_id);
-      for (size_t k = 0; k < nch && e == hipSuccess; ++k) {
-        const uint64_t b0 = hoff[cuts[k]], b1 = hoff[cuts[k + 1]];
-        e = d.stager->put(ddata + b0, data + base + b0, b1 - b0);
-        if (e == hipSuccess) e = d.stager->flush();
-        if (e == hipSuccess) e = hipEventRecord(d.ev_chunk[k], d.xfer);
-        if (k + 1 == nch) tm_copied = std::chrono::steady_clock::now();
-        std::lock_guard<std::mutex> g(cmu);
-        if (e == hipSuccess) recorded = k + 1;
-        else copy_err = e;
-        ccv.notify_all();
-      }
-    });
-    auto chunk_ready = [&](size_t k) -> int {
-      {
-        std::unique_lock<std::mutex> g(cmu);
-        ccv.wait(g, [&] { return recorded > k || copy_err != hipSuccess; });
-        if (recorded <= k) return set_err(NWC_ERR_DEVICE, "message copy: %s", hipGetErrorString(copy_err));
-      }
-      const hipError_t e = hipStreamWaitEvent(d.stream, d.ev_chunk[k], 0);
-      if (e != hipSuccess) return set_err(NWC_ERR_DEVICE, "hipStreamWaitEvent: %s", hipGetErrorString(e));
-      return 0;
-    };
-    auto chunk_queued = [&](size_t k) -> bool {
-      std::lock_guard<std::mutex> g(cmu);
-      return recorded > k;
-    };
-    int rc = sanitize_dev(d, ddata, doff, m, total, cuts, gc_round, vote_target, dcodes, ddig, drec, d.stream,
-                          chunk_ready, chunk_queued);
-    copier.join();   // the copier never waits on this thread: it runs through every chunk
-    if (rc) {
-      (void)hipStreamSynchronize(d.xfer);   // no copy still writes the arena when the call returns
-      return rc;
-    }
-    if (settings().host_timing) {
-      HIP_TRY(hipStreamSynchronize(d.stream));
-      const auto tm1 = std::chrono::steady_clock::now();
-      std::fprintf(stderr, "nwc sanitize: %zu messages, %.1f MB in %zu chunks: copies queued after %.2f ms, pipeline done %.2f ms later\n",
-                   m, total / 1e6, nch, std::chrono::duration<double>(tm_copied - tm0).count() * 1e3,
-                   std::chrono::duration<double>(tm1 - tm_copied).count() * 1e3);
-    }
-  }
-  HIP_TRY(hipMemcpyAsync(codes, dcodes, 4 * m, hipMemcpyDeviceToHost, d.stream));
-  std::vector<uint32_t> rec;
-  if (kinds) {
-    rec.resize(4 * m);
-    HIP_TRY(hipMemcpyAsync(rec.data(), drec, 16 * m, hipMemcpyDeviceToHost, d.stream));
-  }
-  if (digests32) HIP_TRY(hipMemcpyAsync(digests32, ddig, 32 * m, hipMemcpyDeviceToHost, d.stream));
-  HIP_TRY(hipStreamSynchronize(d.stream));
-  if (kinds)
-    for (size_t i = 0; i < m; ++i) kinds[i] = (uint8_t)rec[4 * i];
-  return 0;
-}
-
-int nwc_dev_sanitize_messages(const void* d_data, const void* d_offsets, uint64_t m, uint64_t total,
-                              uint64_t gc_round, const uint8_t* vote_target, void* d_codes, void* d_digests32,
-                              void* stream) {
-  if (int rc = require_init()) return rc;
-  if (m == 0) return 0;
-  if (!d_data || !d_offsets || !d_codes) return set_err(NWC_ERR_ARG, "null buffer");
-  if ((reinterpret_cast<uintptr_t>(d_data) & 3) != 0) return set_err(NWC_ERR_ARG, "d_data must be 4-byte aligned");
-  DevCtx& d = *ctx(t_dev < (int)g_devs.size() ? t_dev : 0);
-  std::lock_guard<std::mutex> lk(d.mu);
-  HIP_TRY(hipSetDevice(d.hip_id));
-  if (!d.cc_stakes) return set_err(NWC_ERR_NOT_INIT, "nwc_set_committee_config has not been called");
-  return sanitize_dev(d, static_cast<const uint8_t*>(d_data), static_cast<const uint64_t*>(d_offsets), m, total,
-                      {0, (size_t)m}, gc_round, vote_target, static_cast<int32_t*>(d_codes), static_cast<uint8_t*>(d_digests32),
-                      nullptr, stream ? static_cast<hipStream_t>(stream) : d.stream);
-}
-
 }  // extern "C"
 
 #include "digester.h"
+#include "sanitizer.h"
 #include "signer.h"
 #include "verifier.h"
 

@@ -193,7 +193,8 @@ def test_sanitize_messages_host_chunks(env):
                        env=dict(os.environ, NWC_MSG_CHUNK=str(1 << 20), NWC_HOST_TIMING="1", **env))
     assert r.returncode == 0 and "done" in r.stdout, (r.returncode, r.stdout[-500:], r.stderr[-3000:])
     steps = [l for l in r.stderr.splitlines() if l.startswith("nwc sanitize steps:")]
-    assert steps and all(l.count("parse queued") >= 4 for l in steps), r.stderr[-2000:]   # several chunks
+    # 8 chunks: what the cut rule (msg_plan.h message_cuts) gives for this batch of a little over 8 MiB at 1 MiB
+    assert steps and all(l.count("parse queued") == 8 for l in steps), r.stderr[-2000:]
 
 
 def _sanitize_tiled_golden():
