@@ -245,6 +245,64 @@ int nwc_verifier_verify_batch(void* verifier, const uint8_t msg32[32], const uin
 int nwc_verifier_stats(void* verifier, uint64_t* out);
 int nwc_verifier_destroy(void* verifier);
 
+/* ---- concurrent wire messages behind one pipeline launch ---------------------------------- */
+/* A primary receives its wire messages one at a time, on one tokio task per peer connection
+ * (PrimaryReceiverHandler::dispatch, primary/src/primary.rs:224-240), and needs the
+ * Core::sanitize_header / sanitize_vote / sanitize_certificate verdict of each before Core may act
+ * on it.  nwc_sanitize_messages (below) is a batch entry: with one message it holds the device for
+ * the whole call and makes two host round trips, so concurrent callers run one after another.  A
+ * sanitizer is an opaque handle (void*, as a verifier) bound to the calling thread's device:
+ * concurrent blocking calls, each carrying ONE bincode PrimaryMessage, are packed into GROUPS; one
+ * fixed set of launches (parse, decide, finalize) decides a group with no host round trip inside
+ * it, and each caller returns as soon as its own result word is in.  Opt-in; the batch entry is
+ * unchanged.
+ *
+ * The code (NWC_DAG_*), digest and kind are exactly those of nwc_sanitize_messages on this message
+ * alone with the same gc_round and vote_target (its DagError precedence; the batch leaves, Err on
+ * the randomized domain).  gc_round and vote_target (72 bytes as there, or NULL) belong to the
+ * request: Core's state moves while messages are in flight, so two messages of one group may carry
+ * different values, and each is judged by its own.
+ *
+ * A group closes when it holds max_messages messages (0 = as many as fit), when the next message's
+ * bytes do not fit, or when max_wait_us have passed since it was opened.  max_wait_us == 0 never
+ * waits for company: a lone caller launches at once, and under load a group is whatever arrived
+ * during the previous flight.  A group holds NWC_SANITIZER_GROUP_BYTES wire bytes (1 MiB, ~100
+ * certificates of a 100-node committee; every message starts 16-byte aligned) and
+ * NWC_SANITIZER_GROUP_MSGS messages (256), both read from the environment by the first create.  A
+ * sanitizer holds two group buffers of coherent pinned host memory, read in place by the kernels,
+ * and one block of HBM scratch (nwc_memory_info: scratch; kept by nwc_trim, released by destroy).
+ *
+ * Conventions as the verifier's: calls block and may be made from any number of threads; a null
+ * sanitizer, or a null msg with len > 0, gives NWC_ERR_ARG; len == 0 is a message of no bytes
+ * (NWC_DAG_SERIALIZATION_ERROR) as in the batch entry; NWC_ERR_NOT_INIT before nwc_init and before
+ * nwc_set_committee_config (create then returns NULL).  A message larger than a group is handed to
+ * nwc_sanitize_messages (bypassed_messages), and so is every message while the grouped kernels'
+ * preconditions do not hold: the committee cache is the configured committee
+ * (nwc_set_committee_config was the last to set it) and has its combs (<= 1,024 keys), NWC_COLD
+ * and NWC_VERIFY_PATH at their defaults.  A device error in a group reaches exactly that group's
+ * callers as a code < 0, never as a NWC_DAG_* code.  destroy lets queued requests finish, wakes
+ * blocked callers and waits for them to leave (no call on the sanitizer may start after destroy);
+ * nwc_shutdown does the same to sanitizers still alive, which then answer NWC_ERR_NOT_INIT; destroy
+ * them afterwards all the same.  create returns NULL on failure (nwc_last_error,
+ * nwc_last_error_code). */
+typedef struct nwc_sanitizer_stats_t {
+  uint64_t groups, messages, bytes, equations, redone_messages, bypassed_messages,
+      max_messages_in_group, reserved;
+} nwc_sanitizer_stats_t;
+void* nwc_sanitizer_create(uint32_t max_messages, uint32_t max_wait_us);
+/* Core::sanitize_header / sanitize_vote / sanitize_certificate of ONE wire message.
+ * Returns NWC_DAG_* (>= 0) or an error < 0.  digest32, kind nullable. */
+int nwc_sanitizer_sanitize(void* sanitizer, const uint8_t* msg, size_t len, uint64_t gc_round,
+                           const uint8_t* vote_target, uint8_t digest32[32], uint8_t* kind);
+/* out: eight uint64_t laid out as nwc_sanitizer_stats_t.  messages / bytes are counted when a
+ * message joins a group, groups / max_messages_in_group when a group launches, equations (the
+ * signature equations the groups decided: a message's own once every earlier check of its
+ * precedence chain but Header::digest has passed, a certificate's votes once its vote list is
+ * sound) and redone_messages (messages decided again by nwc_sanitize_messages: the result word
+ * asked for it or was still unwritten after the stream had been waited for) when a caller leaves. */
+int nwc_sanitizer_stats(void* sanitizer, uint64_t* out);
+int nwc_sanitizer_destroy(void* sanitizer);
+
 /* Committee key cache (config/src/lib.rs:154-156 Committee).  Optional: verdicts never
  * depend on it. */
 int nwc_set_committee(const uint8_t* pks, size_t n);

@@ -61,6 +61,11 @@ _SIGS = {
     "nwc_verifier_verify_batch": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, _c_u8p, _c_u8p, ctypes.c_size_t, _c_u8p]),
     "nwc_verifier_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "nwc_verifier_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "nwc_sanitizer_create": (ctypes.c_void_p, [ctypes.c_uint32, ctypes.c_uint32]),
+    "nwc_sanitizer_sanitize": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, ctypes.c_size_t, ctypes.c_uint64, _c_u8p, _c_u8p,
+                                              _c_u8p]),
+    "nwc_sanitizer_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nwc_sanitizer_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "nwc_set_committee": (ctypes.c_int, [_c_u8p, ctypes.c_size_t]),
     "nwc_cache_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "nwc_auto_cache_info": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),

@@ -14,6 +14,11 @@
 //   k_header_digests     one lane per message: Header::digest of the gathered input vs the id.
 //   k_finalize_messages  combines the flags with the equation verdicts into the DagError the
 //                        reference returns, in its order (primary/src/error.rs).
+//   k_parse_group, k_verify_msg_group, k_finalize_group
+//                        the same three steps for a GROUP of one-message calls (nwc_sanitizer,
+//                        sanitizer_handle.h): every message under its own gc_round and vote
+//                        target, the equations a verdict can depend on listed on the device, no
+//                        host read between the first launch and the result words (see below).
 //
 // Wire layout (bincode of PrimaryMessage, primary/src/primary.rs:33-38):
 //   u32 variant (0 Header, 1 Vote, 2 Certificate, 3 CertificatesRequest)
@@ -459,12 +464,35 @@ __device__ uint64_t canon_entries(const uint8_t* base, uint64_t src, uint64_t cn
 // instructions, no divergence); vote-, payload- and digest-input loops are split across lanes.
 // Dynamic LDS: one word per committee member (4 * min(cc.n, MSG_MAX_COMMITTEE) bytes, at least 4), so
 // a 100-node committee takes 400 B per wave and the kernel's occupancy is set by its VGPRs.
-__global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, CommitteeCfg cc) {
-  extern __shared__ u32 first[];   // first vote position of each committee member
-  const uint64_t i = blockIdx.x;
-  const u32 lane = threadIdx.x;
-  if (i >= a.m) return;   // block-uniform
-  MsgReader r{a.data, a.offsets[i], a.offsets[i + 1], true, false};
+
+// What parse_message decided about its message (the same in every lane): the record it stored.
+struct MsgParsed { u32 kind, flags, post, vbase, vcount; };
+// Where a message's bytes lie and what it is judged by.  k_parse_messages: the launch's offsets,
+// gc_round and vote target (read from the kernel's arguments where they are used, as before the
+// body was shared); k_parse_group: the message's own.
+struct UniformMsg {
+  const MsgArgs& a;
+  const uint64_t i;
+  __device__ __forceinline__ uint64_t beg() const { return a.offsets[i]; }
+  __device__ __forceinline__ uint64_t end() const { return a.offsets[i + 1]; }
+  __device__ __forceinline__ uint64_t gc_round() const { return a.gc_round; }
+  __device__ __forceinline__ const VoteTarget& target() const { return a.target; }
+};
+struct OwnMsg {
+  const uint64_t b, e, gc;
+  const VoteTarget& t;
+  __device__ __forceinline__ uint64_t beg() const { return b; }
+  __device__ __forceinline__ uint64_t end() const { return e; }
+  __device__ __forceinline__ uint64_t gc_round() const { return gc; }
+  __device__ __forceinline__ const VoteTarget& target() const { return t; }
+};
+
+// The body of k_parse_messages and k_parse_group: message i of the launch, bytes
+// [src.beg(), src.end()) of a.data; `first` is the wave's dynamic LDS.
+template <class Src>
+__device__ __forceinline__ MsgParsed parse_message(const MsgArgs& a, const Committee& cm, const CommitteeCfg& cc, u32* first,
+                                                   const uint64_t i, const u32 lane, const Src& src) {
+  MsgReader r{a.data, src.beg(), src.end(), true, false};
   const uint64_t variant = ld_u32(a.data, r.pos);
   r.need(4);
   r.pos += 4;
@@ -491,7 +519,7 @@ __global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, 
     const uint64_t astake = member_stake(cc, aidx);
     // per-message scratch (>= message length + 1 bytes, 128-B aligned): the Header::digest input
     // (author || round || BTreeMap payload || BTreeSet parents), then the vote offsets
-    u32* d = reinterpret_cast<u32*>(a.hashbuf + ((a.offsets[i] + 127) & ~(uint64_t)127) + 128 * i);
+    u32* d = reinterpret_cast<u32*>(a.hashbuf + ((src.beg() + 127) & ~(uint64_t)127) + 128 * i);
     if (r.ok) {
       if (lane == 0) {
         _Pragma("unroll") for (int k = 0; k < 8; ++k) d[k] = author[k];
@@ -625,7 +653,7 @@ __global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, 
       u32 z = 0;
       _Pragma("unroll") for (int k = 0; k < 8; ++k) z |= id[k];
       if (kind == MSG_CERTIFICATE && round == 0 && aidx >= 0 && z == 0) flags |= MF_GENESIS;
-      if (a.gc_round > round) flags |= MF_TOO_OLD;
+      if (src.gc_round() > round) flags |= MF_TOO_OLD;
       if (astake == 0) flags |= MF_STAKE0;
     }
     _Pragma("unroll") for (int k = 0; k < 8; ++k) { eq_msg[k] = id[k]; eq_pk[k] = author[k]; dig[k] = cd[k]; }
@@ -640,10 +668,10 @@ __global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, 
     digest72(id, round, origin, dig);
     if (!r.ok) {
       flags |= MF_PARSE_ERR | (r.panic ? MF_PANIC : 0u);
-    } else if (a.target.enabled && a.target.round > round) {
+    } else if (src.target().enabled && src.target().round > round) {
       post = DAG_TOO_OLD;   // Core::sanitize_vote (primary/src/core.rs:319-322)
-    } else if (a.target.enabled && !(words_eq8(id, a.target.id) && words_eq8(origin, a.target.origin) &&
-                                     round == a.target.round)) {
+    } else if (src.target().enabled && !(words_eq8(id, src.target().id) && words_eq8(origin, src.target().origin) &&
+                                         round == src.target().round)) {
       post = DAG_UNEXPECTED_VOTE;   // core.rs:325-330
     } else if (member_stake(cc, committee_lookup(cm, author)) == 0) {
       post = DAG_UNKNOWN_AUTHORITY;   // Vote::verify (messages.rs:133-136)
@@ -665,12 +693,19 @@ __global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, 
     a.rec[4 * i + 3] = hlen;
     a.rec_n[i] = vcount;
   }
+  return MsgParsed{kind, flags, post, vbase, vcount};
+}
+
+__global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, CommitteeCfg cc) {
+  extern __shared__ u32 first[];   // first vote position of each committee member
+  const uint64_t i = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= a.m) return;   // block-uniform
+  (void)parse_message(a, cm, cc, first, i, lane, UniformMsg{a, i});
 }
 
 // Header::digest of the gathered input, one lane per message (a header of 67 parents is 18 blocks)
-__global__ __launch_bounds__(256) void k_header_digests(MsgArgs a) {
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= a.m) return;
+__device__ __forceinline__ void header_digest_one(const MsgArgs& a, const uint64_t i) {
   const u32 r0 = a.rec[4 * i], kind = r0 & 255u;
   u32 match = 0;
   if ((kind == MSG_HEADER || kind == MSG_CERTIFICATE) && !(r0 & MF_PARSE_ERR)) {
@@ -686,6 +721,160 @@ __global__ __launch_bounds__(256) void k_header_digests(MsgArgs a) {
     st_words(a.digests + 32 * i, z, 8);
   }
   a.hmatch[i] = match;
+}
+__global__ __launch_bounds__(256) void k_header_digests(MsgArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= a.m) return;
+  header_digest_one(a, i);
+}
+
+// ---- groups of one-message calls (sanitizer_handle.h, sanitize_queue.h) ------------------------
+// A group's messages lie in one pinned host buffer, message i at bytes [starts[i], starts[i] +
+// lens[i]) of a.data (every start 16-byte aligned) with its own gc_round and vote target (80 bytes:
+// id, round, origin, then the "enabled" byte).  The group's equations share one index space of
+// max_msgs + a.v_cap entries: message i's strict equation is entry i, vote slot v is entry
+// max_msgs + v (the host points a.v_* at entry max_msgs of the a.eq_* arrays and sets
+// a.msg_base = max_msgs, so the parse body's stores land there and a vote's digest index selects
+// a.cdig, which follows a.eq_msg).  One fixed sequence of launches decides a group:
+//   k_parse_group       parse_message per message, then the equations a verdict can depend on are
+//                       appended to `list` (count in device memory);
+//   k_verify_msg_group  verify_wide_body over list[b], the Header::digest checks in its first blocks;
+//   k_finalize_group    k_finalize_messages' precedence over the verdict bytes; digest, kind and
+//                       the result word go to the pinned buffer.
+struct GroupMsgs {
+  const uint64_t* starts;
+  const uint32_t* lens;
+  const uint64_t* gc_rounds;
+  const uint8_t* targets;
+  uint32_t* list;         // max_msgs + v_cap entries
+  uint32_t* list_count;
+  uint32_t max_msgs, nmsg;
+};
+constexpr u32 GROUP_TARGET_STRIDE = 80;
+constexpr u32 GROUP_WRITTEN = 1u << 31, GROUP_REDO = 1u << 30;
+
+// Which equations a message's verdict can depend on, from what the parse knows (everything of the
+// precedence chain before the signatures but Header::digest == id): bit 0 its strict equation,
+// bit 1 its votes' (a certificate whose post code is Ok).  k_finalize_group reads exactly these.
+__device__ __forceinline__ u32 msg_lists(u32 kind, u32 flags, u32 post) {
+  if (kind == MSG_OTHER || (flags & MF_PARSE_ERR)) return 0;
+  if (kind == MSG_VOTE) return post == DAG_OK ? 1u : 0u;
+  if (flags & (MF_TOO_OLD | MF_STAKE0 | MF_WORKER_BAD)) return 0;
+  if (kind == MSG_CERTIFICATE && (flags & MF_GENESIS)) return 0;
+  if (kind == MSG_HEADER) return 1;
+  return post == DAG_OK ? 3u : 1u;
+}
+
+__global__ __launch_bounds__(64) void k_parse_group(MsgArgs a, Committee cm, CommitteeCfg cc, GroupMsgs g) {
+  extern __shared__ u32 first[];
+  const uint64_t i = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= g.nmsg) return;   // block-uniform
+  const uint64_t beg = g.starts[i], end = beg + g.lens[i];
+  const u32* tw = reinterpret_cast<const u32*>(g.targets + (size_t)GROUP_TARGET_STRIDE * i);
+  VoteTarget t;
+  _Pragma("unroll") for (int k = 0; k < 8; ++k) { t.id[k] = tw[k]; t.origin[k] = tw[10 + k]; }
+  t.round = (uint64_t)tw[8] | ((uint64_t)tw[9] << 32);
+  t.enabled = (int)(tw[18] & 1u);
+  const MsgParsed p = parse_message(a, cm, cc, first, i, lane, OwnMsg{beg, end, g.gc_rounds[i], t});
+  const u32 what = msg_lists(p.kind, p.flags, p.post);
+  if (!what) return;   // wave-uniform
+  const u32 nv = (what & 2u) ? p.vcount : 0u;
+  u32 base = 0;
+  if (lane == 0) {
+    base = atomicAdd(g.list_count, 1u + nv);
+    g.list[base] = (u32)i;
+  }
+  base = (u32)__shfl((int)base, 0, 64);
+  for (u32 v = lane; v < nv; v += 64) g.list[base + 1 + v] = g.max_msgs + p.vbase + v;
+}
+
+struct MsgGroupArgs {
+  const uint32_t* list;
+  const uint32_t* count;
+  const uint8_t* modes;
+  uint8_t* vbytes;         // one verdict byte per entry: bit 7 written, bit 0 valid, bit 1 = decide me again
+  uint32_t hd_blocks;      // the first hd_blocks blocks run Header::digest, one lane per message (0: none)
+};
+__global__ __launch_bounds__(128) void k_verify_msg_group(VerifyArgs a, CombArgs ca, MsgGroupArgs g, MsgArgs ma) {
+  __shared__ fe sh_rx, sh_ry;
+  __shared__ int sh_rok;
+  if (blockIdx.x < g.hd_blocks) {   // block-uniform
+    const uint64_t i = (uint64_t)blockIdx.x * 128 + threadIdx.x;
+    if (i < ma.m) header_digest_one(ma, i);
+    return;
+  }
+  const uint32_t b = blockIdx.x - g.hd_blocks;
+  if (b >= *g.count) return;        // block-uniform
+  const uint32_t e = g.list[b];
+  if (e >= a.n) return;             // block-uniform; never indexes past the group's arrays
+  const int mode = __builtin_amdgcn_readfirstlane((int)(g.modes[e] & 1u));
+  verify_wide_body(a, ca, g.vbytes, e, mode, sh_rx, sh_ry, sh_rok);
+}
+
+struct GroupOut {
+  uint32_t* results;   // pinned: bit 31 written, bit 30 decide me again, bits 8-23 equations listed, bits 0-7 code
+  uint8_t* digests;    // pinned, 32 B per message
+  uint8_t* kinds;      // pinned
+};
+// redo_every (nwc_diag_set "sanitizer_redo_every"): message slots i with i % redo_every == 0 are
+// marked "decide me again" (0 = off).  The last thing the group does is to zero its two counters
+// (the vote-slot allocator and the list count) for the next group on the stream.
+__global__ void k_finalize_group(const uint32_t* __restrict__ rec, const uint32_t* __restrict__ rec_n,
+                                 const uint32_t* __restrict__ hmatch, const uint8_t* __restrict__ vbytes,
+                                 const uint8_t* __restrict__ digests, uint32_t max_msgs, uint32_t nmsg, GroupOut out,
+                                 uint32_t redo_every, uint32_t* v_total, uint32_t* list_count) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    *v_total = 0;
+    *list_count = 0;
+  }
+  if (i >= nmsg) return;
+  const u32 r0 = rec[4 * i], kind = r0 & 255u, flags = r0 & ~255u, post = rec[4 * i + 1], vbase = rec[4 * i + 2];
+  const u32 vn = rec_n[i];
+  const u32 what = msg_lists(kind, flags, post);
+  bool again = redo_every && i % redo_every == 0;
+  auto valid = [&](u32 e) {
+    const u32 v = vbytes[e];
+    again = again || !(v & 0x80u) || (v & 2u);
+    return (v & 1u) != 0;
+  };
+  u32 code;
+  if (kind == MSG_OTHER) {
+    code = post;
+  } else if (r0 & MF_PARSE_ERR) {
+    code = (r0 & MF_PANIC) ? DAG_DECODE_PANIC : DAG_SERIALIZATION;
+  } else if (kind == MSG_VOTE) {
+    code = post != DAG_OK ? post : (valid(i) ? DAG_OK : DAG_INVALID_SIGNATURE);
+  } else if (r0 & MF_TOO_OLD) {
+    code = DAG_TOO_OLD;
+  } else if (kind == MSG_CERTIFICATE && (r0 & MF_GENESIS)) {
+    code = DAG_OK;
+  } else if (!hmatch[i]) {
+    code = DAG_INVALID_HEADER_ID;
+  } else if (r0 & MF_STAKE0) {
+    code = DAG_UNKNOWN_AUTHORITY;
+  } else if (r0 & MF_WORKER_BAD) {
+    code = DAG_MALFORMED_HEADER;
+  } else if (!valid(i)) {
+    code = DAG_INVALID_SIGNATURE;
+  } else if (kind == MSG_HEADER) {
+    code = DAG_OK;
+  } else if (post != DAG_OK) {
+    code = post;
+  } else {
+    bool all = true;
+    for (u32 v = 0; v < vn; ++v) all = valid(max_msgs + vbase + v) && all;
+    code = all ? DAG_OK : DAG_INVALID_SIGNATURE;
+  }
+  const u32 neq = (what & 1u) + ((what & 2u) ? vn : 0u);
+  const u32* dw = reinterpret_cast<const u32*>(digests + 32 * (size_t)i);
+  u32* ow = reinterpret_cast<u32*>(out.digests + 32 * (size_t)i);
+  _Pragma("unroll") for (int k = 0; k < 8; ++k) ow[k] = dw[k];
+  out.kinds[i] = (uint8_t)kind;
+  // system scope, release: the poller sees the digest and the kind once it sees the word
+  __hip_atomic_store(out.results + i, GROUP_WRITTEN | (again ? GROUP_REDO : 0u) | ((neq < 0xFFFFu ? neq : 0xFFFFu) << 8) | (code & 255u),
+                     __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // code[i] in the reference's order:

@@ -132,6 +132,61 @@ inline MsgArena msg_arena(size_t m, uint64_t total, uint64_t vt, bool ysplit, bo
   return a;
 }
 
+// A sanitizer handle's buffers (sanitizer_handle.h; byte offsets), for groups of up to max_msgs
+// messages in byte_cap wire bytes.  The group's equations share one index space of
+// entries = max_msgs + vote_slots(byte_cap, 1): message i's strict equation at i, vote slot v at
+// max_msgs + v.
+//   SanGroupBuf: one pinned group buffer -- the wire bytes with 16 bytes of readable padding, the
+//     per-message starts, lengths, gc_rounds and vote targets (80 B), and on the way back the result
+//     words, digests and kinds.
+//   SanScratch: the HBM scratch of the handle (one group runs at a time on the device's stream).
+//     eq_msg is followed by cdig (one digest array of 2 x max_msgs); `counters` is the vote-slot
+//     allocator and the list count.
+struct SanGroupBuf {
+  size_t data, starts, lens, gc_rounds, targets, results, digests, kinds;
+  size_t bytes;
+};
+inline SanGroupBuf san_group_buf(size_t max_msgs, uint64_t byte_cap) {
+  ArenaWalk w;
+  SanGroupBuf a;
+  a.data = w.take(byte_cap + 16);
+  a.starts = w.take(8 * max_msgs);
+  a.lens = w.take(4 * max_msgs);
+  a.gc_rounds = w.take(8 * max_msgs);
+  a.targets = w.take(80 * max_msgs);
+  a.results = w.take(4 * max_msgs);
+  a.digests = w.take(32 * max_msgs);
+  a.kinds = w.take(max_msgs);
+  a.bytes = w.off;
+  return a;
+}
+struct SanScratch {
+  size_t hashbuf, eq_msg, eq_pk, eq_sig, msg_index, modes, vbytes, list, counters, hmatch, rec, rec_n, digests;
+  uint64_t vote_slots, entries;
+  size_t bytes;
+};
+inline SanScratch san_scratch(size_t max_msgs, uint64_t byte_cap) {
+  ArenaWalk w;
+  SanScratch a{};
+  a.vote_slots = vote_slots(byte_cap, 1);
+  a.entries = max_msgs + a.vote_slots;
+  a.hashbuf = w.take(byte_cap + 128 * (max_msgs + 2));
+  a.eq_msg = w.take(64 * max_msgs);
+  a.eq_pk = w.take(32 * a.entries);
+  a.eq_sig = w.take(64 * a.entries);
+  a.msg_index = w.take(4 * a.entries);
+  a.modes = w.take(a.entries);
+  a.vbytes = w.take(a.entries);
+  a.list = w.take(4 * a.entries);
+  a.counters = w.take(8);
+  a.hmatch = w.take(4 * max_msgs);
+  a.rec = w.take(16 * max_msgs);
+  a.rec_n = w.take(4 * max_msgs);
+  a.digests = w.take(32 * max_msgs);
+  a.bytes = w.off;
+  return a;
+}
+
 // The pinned stage as the message pipeline uses it: the chunks' vote counts (uint32 each, read
 // back asynchronously) in the first 64 KiB, the host call's message offsets above them.
 constexpr size_t STAGE_COUNTS_AT = 0, STAGE_COUNTS_BYTES = 64u << 10;

@@ -299,6 +299,7 @@ struct Carve {
 
 void signers_shutdown();
 void verifiers_shutdown();
+void sanitizers_shutdown();
 int auto_grow(DevCtx& d, uint32_t ncap);
 
 // Test and A/B knobs settable at run time (nwc_diag_set), defaults from the environment (settings()):
@@ -311,6 +312,7 @@ struct Knobs {
   std::atomic<uint32_t> msm_group{0};     // NWC_MSM_GROUP: votes per Pippenger group of k_verify_msm (0 = sized per launch)
   std::atomic<uint32_t> msm_adapt{1};     // NWC_MSM_ADAPT: 0 = the equation on every group (no skip policy)
   std::atomic<uint32_t> sign_path{0};     // tests: 0 = by size (NWC_SIGN_WIDE_MAX), 1 = k_sign, 2 = k_sign_wide
+  std::atomic<uint32_t> sanitizer_redo_every{0};   // tests: k_finalize_group marks message slots i % k == 0 "decide me again" (0 = off)
   std::atomic<uint64_t> dalek_seed{0};    // tests: fixed seed of the per-certificate equation's z_i (0 = host CSPRNG)
   Knobs() {
     const nwc::plan::Settings& s = settings();
@@ -1809,6 +1811,8 @@ int nwc_diag_set(const char* name, int64_t value) {
     knobs().msm_adapt = (uint32_t)value;
   } else if (std::strcmp(name, "dalek_seed") == 0) {
     knobs().dalek_seed = (uint64_t)value;
+  } else if (std::strcmp(name, "sanitizer_redo_every") == 0) {
+    knobs().sanitizer_redo_every = (uint32_t)value;
   } else if (std::strcmp(name, "sign_path") == 0) {
     if (value > 2) return set_err(NWC_ERR_ARG, "sign_path must be 0 (by size), 1 (k_sign) or 2 (k_sign_wide)");
     knobs().sign_path = (uint32_t)value;
@@ -1869,6 +1873,7 @@ void nwc_shutdown(void) {
   std::lock_guard<std::mutex> lk(g_mu);
   signers_shutdown();   // live signers' key records are zeroed and freed first
   verifiers_shutdown();  // live verifiers finish what is queued; their pinned group buffers go
+  sanitizers_shutdown(); // and live sanitizers: their pinned group buffers and their HBM scratch
   for (auto& d : g_devs) {
     std::lock_guard<std::mutex> dl(d->mu);
     (void)hipSetDevice(d->hip_id);
@@ -2020,6 +2025,9 @@ static int set_committee_locked(const uint8_t* pks, size_t n);
 // undecided -- their authors are outside the committee, and UnknownAuthority precedes
 // InvalidSignature for every message kind (primary/src/core.rs, messages.rs).
 std::atomic<bool> g_cm_is_config{false};
+// Every device's committee cache holds keys with their per-key combs (the latency kernels'
+// precondition; read without a context's mu by sanitizer_handle.h).
+std::atomic<bool> g_cm_combs{false};
 
 int nwc_set_committee(const uint8_t* pks, size_t n) {
   std::lock_guard<std::mutex> lk(g_cm_mu);
@@ -2036,6 +2044,7 @@ static int set_committee_locked(const uint8_t* pks, size_t n) {
   std::memcpy(keys.data(), pks, 32 * n);
   std::vector<int32_t> table;
   const uint32_t slots = build_slots(keys, n, table);
+  g_cm_combs = false;
   {
     // host view cleared while the devices change (a call in between takes the general path),
     // set again once every device holds the new cache (end of this function)
@@ -2086,6 +2095,7 @@ static int set_committee_locked(const uint8_t* pks, size_t n) {
     g_hcm.idx.slots = table;
     g_hcm.idx.mask = slots - 1;
   }
+  g_cm_combs = n > 0 && n <= NWC_COMB_MAX_KEYS;
   return 0;
 }
 
@@ -2395,6 +2405,7 @@ int nwc_set_committee_config(const uint8_t* pks, const uint64_t* stakes, size_t 
 #include "sanitizer.h"
 #include "signer.h"
 #include "verifier.h"
+#include "sanitizer_handle.h"
 
 extern "C" {
 

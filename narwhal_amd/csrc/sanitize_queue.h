@@ -1,0 +1,329 @@
+// Group formation for concurrent one-message sanitize calls (nwc_sanitizer, sanitizer_handle.h):
+// blocking requests from many threads, each carrying one wire message, are packed into shared
+// pipeline launches.  No HIP in here -- like verify_queue.h, the queue drives a Backend ("launch
+// this group", "wait for it", "decide this message again"), so that it runs against a fake backend
+// under the host sanitizers (tests/cpp/sanitize_queue_host.cpp).
+//
+// A group is the set of requests that share one set of launches.  It lives in one of the backend's
+// group buffers: a request reserves a message slot and a byte range in the open group under the
+// queue lock -- the range starts 16-byte aligned, as a digester arena batch does -- and outside the
+// lock copies its bytes, its gc_round and its vote target there and clears its result word.  The
+// thread that opened the group is its leader: it waits for the group to close, for the members'
+// copies to finish, and launches; every member then polls its own result word (bit 31 written, bit
+// 30 "decide me again", bits 8-23 the equations the message listed, bits 0-7 the code) and leaves
+// as soon as it is in.  The buffer is free again when the last member has left.
+//
+// A group closes when it holds max_messages messages, when the next message's bytes do not fit,
+// when max_wait_us have passed since it was opened, or -- max_wait_us == 0 -- as soon as no earlier
+// group is in flight: a lone caller launches at once, and under load a group is whatever arrived
+// while the previous one was busy.
+#pragma once
+
+#include <atomic>
+#include <chrono>
+#include <condition_variable>
+#include <cstdint>
+#include <cstring>
+#include <mutex>
+#include <thread>
+#include <vector>
+
+#include "nwc.h"
+
+namespace nwc {
+namespace sq {
+
+constexpr uint32_t R_WRITTEN = 1u << 31, R_REDO = 1u << 30;
+constexpr size_t TARGET_STRIDE = 80;   // id(32) round(8, LE) origin(32), then the "enabled" byte
+constexpr size_t TARGET_FLAG_AT = 72;
+constexpr uint64_t RANGE_ALIGN = 16;
+
+inline uint64_t align_range(uint64_t x) { return (x + (RANGE_ALIGN - 1)) & ~(RANGE_ALIGN - 1); }
+inline uint32_t result_code(uint32_t w) { return w & 255u; }
+inline uint32_t result_equations(uint32_t w) { return (w >> 8) & 0xFFFFu; }
+
+// Host pointers into one group buffer of `byte_cap` wire bytes and `max_messages` messages.
+struct GroupBuf {
+  uint8_t* data = nullptr;        // wire bytes; at least 16 readable bytes follow byte_cap
+  uint64_t* starts = nullptr;     // per message: where its bytes begin in data (16-byte aligned)
+  uint32_t* lens = nullptr;       // per message: its length
+  uint64_t* gc_rounds = nullptr;  // per message
+  uint8_t* targets = nullptr;     // per message, TARGET_STRIDE bytes
+  uint32_t* results = nullptr;    // per message: the result word
+  uint8_t* digests = nullptr;     // per message, 32 B: written before the result word
+  uint8_t* kinds = nullptr;       // per message: written before the result word
+};
+
+struct Backend {
+  virtual ~Backend() = default;
+  virtual GroupBuf buffer(int b) = 0;
+  // Enqueue the work that decides messages [0, nmsg) of buffer b (bytes [0, nbytes) of its data)
+  // and return without waiting for it.  0, or an error < 0 that every member of the group receives.
+  virtual int launch(int b, uint32_t nmsg, uint64_t nbytes) = 0;
+  // Wait for everything launched for buffer b (a member's poll timed out): 0, or the error < 0.
+  virtual int wait(int b) = 0;
+  // Decide one message again, outside the group: the code >= 0, or an error < 0.
+  virtual int redo(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32,
+                   uint8_t* kind) = 0;
+  // A message that does not go through a group (larger than one, or the caller asked): as redo.
+  virtual int bypass(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32,
+                     uint8_t* kind) = 0;
+};
+
+struct Stats {
+  uint64_t groups = 0, messages = 0, bytes = 0, equations = 0, redone_messages = 0, bypassed_messages = 0,
+           max_messages_in_group = 0, reserved = 0;
+};
+
+class Queue {
+ public:
+  using clock = std::chrono::steady_clock;
+
+  // nbuf >= 2 group buffers of byte_cap bytes and msg_cap messages; a group closes at max_messages
+  // (0 or more than msg_cap: msg_cap); poll_timeout: how long a member polls before it asks the
+  // backend to wait.
+  Queue(Backend& be, uint32_t nbuf, uint32_t max_messages, uint32_t msg_cap, uint64_t byte_cap, uint32_t max_wait_us,
+        std::chrono::microseconds poll_timeout = std::chrono::milliseconds(200))
+      : be_(be), groups_(nbuf < 2 ? 2 : nbuf), max_msg_(max_messages == 0 || max_messages > msg_cap ? msg_cap : max_messages),
+        byte_cap_(byte_cap), max_wait_(max_wait_us), poll_timeout_(poll_timeout) {}
+
+  uint32_t max_messages() const { return max_msg_; }
+  uint64_t byte_capacity() const { return byte_cap_; }
+
+  // One request: one wire message under its own gc_round and vote target (72 bytes or nullptr).
+  // Returns the message's code >= 0 (digest32 and kind, both nullable, filled), or an error < 0
+  // (the group's launch failed, the device reported an error, or the queue was stopped:
+  // NWC_ERR_NOT_INIT).  direct: hand the message to Backend::bypass whatever its size.
+  int submit(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32, uint8_t* kind,
+             bool direct = false) {
+    std::unique_lock<std::mutex> lk(mu_);
+    if (stopping_) return NWC_ERR_NOT_INIT;
+    ++users_;
+    int rc;
+    if (direct || len > byte_cap_) {
+      ++stats_.bypassed_messages;
+      lk.unlock();
+      rc = be_.bypass(msg, len, gc_round, vote_target, digest32, kind);
+      lk.lock();
+    } else {
+      rc = grouped(lk, msg, len, gc_round, vote_target, digest32, kind);
+    }
+    if (--users_ == 0) signal();
+    return rc;
+  }
+
+  // destroy / shutdown: open groups close at once, queued requests finish, later ones are refused;
+  // returns when every caller has left.
+  void stop() {
+    std::unique_lock<std::mutex> lk(mu_);
+    stopping_ = true;
+    signal();
+    await(lk, [&] { return users_ == 0; });
+  }
+
+  Stats stats() {
+    std::lock_guard<std::mutex> lk(mu_);
+    return stats_;
+  }
+
+ private:
+  enum State { FREE, OPEN, CLOSED, LAUNCHED, FAILED };
+  struct Group {
+    State state = FREE;
+    uint32_t nmsg = 0;
+    uint64_t nbytes = 0;    // end of the last reserved range
+    uint32_t copying = 0;   // members still copying their inputs in
+    uint32_t refs = 0;      // members that have not left
+    int rc = 0;             // FAILED: what every member returns
+    clock::time_point t_open, t_launch;
+  };
+
+  // every state change happens under mu_ and ends in signal(); a waiter spins on the epoch for a
+  // short while (a group's flight time) before it sleeps on the condition variable
+  void signal() {
+    epoch_.fetch_add(1, std::memory_order_release);
+    cv_.notify_all();
+  }
+  // one step of a spin: a pause, and every 256th step the processor to whoever waits for it
+  static void relax(uint32_t k) {
+    if ((k & 255) == 255) std::this_thread::yield();
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#endif
+  }
+  // returns false if `deadline` passed before the state changed
+  bool nap(std::unique_lock<std::mutex>& lk, const clock::time_point* deadline) {
+    const uint64_t e = epoch_.load(std::memory_order_relaxed);
+    lk.unlock();
+    bool changed = false;
+    for (int k = 0; k < 4096 && !changed; ++k) {
+      relax(k);
+      changed = epoch_.load(std::memory_order_acquire) != e;
+      if (deadline && (k & 63) == 63 && clock::now() >= *deadline) break;
+    }
+    lk.lock();
+    auto moved = [&] { return epoch_.load(std::memory_order_relaxed) != e; };
+    if (moved()) return true;
+    if (!deadline) {
+      cv_.wait(lk, moved);
+      return true;
+    }
+    // (a timed wait on the system clock: pthread_cond_timedwait, which every thread sanitizer
+    // runtime knows; a jump of that clock only cuts this nap short or lets the next one end it)
+    const auto left = *deadline - clock::now();
+    if (left <= clock::duration::zero()) return false;
+    return cv_.wait_until(lk, std::chrono::system_clock::now() + left, moved);
+  }
+  template <class P>
+  void await(std::unique_lock<std::mutex>& lk, P pred) {
+    while (!pred()) nap(lk, nullptr);
+  }
+
+  void close(Group& g) {
+    g.state = CLOSED;
+    open_ = -1;
+    signal();
+  }
+
+  int grouped(std::unique_lock<std::mutex>& lk, const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target,
+              uint8_t* digest32, uint8_t* kind) {
+    // a place in the open group, or a free buffer to open the next one in
+    int b = -1;
+    bool leader = false;
+    for (;;) {
+      if (open_ >= 0) {
+        Group& o = groups_[open_];
+        if (o.nmsg < max_msg_ && align_range(o.nbytes) + len <= byte_cap_) { b = open_; break; }
+        close(o);   // full, or this message does not fit: its leader launches it
+      }
+      for (size_t k = 0; k < groups_.size() && b < 0; ++k)
+        if (groups_[k].state == FREE) b = (int)k;
+      if (b >= 0) {
+        Group& f = groups_[b];
+        f = Group{};
+        f.state = OPEN;
+        f.t_open = clock::now();
+        open_ = b;
+        leader = true;
+        break;
+      }
+      nap(lk, nullptr);   // every buffer busy
+    }
+    Group& g = groups_[b];
+    const uint64_t lo = align_range(g.nbytes);
+    const uint32_t slot = g.nmsg;
+    g.nbytes = lo + len;
+    ++g.nmsg;
+    ++g.refs;
+    ++g.copying;
+    ++stats_.messages;        // counted on arrival: a caller can see who is already waiting in a group
+    stats_.bytes += len;
+    if (g.nmsg == max_msg_) close(g);
+    lk.unlock();
+    const GroupBuf gb = be_.buffer(b);
+    if (len) std::memcpy(gb.data + lo, msg, len);
+    gb.starts[slot] = lo;
+    gb.lens[slot] = (uint32_t)len;
+    gb.gc_rounds[slot] = gc_round;
+    uint8_t* t = gb.targets + TARGET_STRIDE * (size_t)slot;
+    if (vote_target) std::memcpy(t, vote_target, TARGET_FLAG_AT);
+    else std::memset(t, 0, TARGET_FLAG_AT);
+    std::memset(t + TARGET_FLAG_AT, 0, TARGET_STRIDE - TARGET_FLAG_AT);
+    t[TARGET_FLAG_AT] = vote_target ? 1 : 0;
+    __atomic_store_n(gb.results + slot, 0u, __ATOMIC_RELAXED);
+    lk.lock();
+    if (--g.copying == 0) signal();
+
+    if (leader) {
+      while (g.state == OPEN) {
+        if (stopping_) {
+          close(g);
+        } else if (max_wait_ == 0) {
+          if (!busy_other(g)) close(g);
+          else nap(lk, nullptr);
+        } else {
+          const clock::time_point deadline = g.t_open + std::chrono::microseconds(max_wait_);
+          if (clock::now() >= deadline) close(g);
+          else nap(lk, &deadline);
+        }
+      }
+      await(lk, [&] { return g.copying == 0; });
+      const uint32_t nmsg = g.nmsg;
+      const uint64_t nbytes = g.nbytes;
+      lk.unlock();
+      const int lrc = be_.launch(b, nmsg, nbytes);
+      lk.lock();
+      g.t_launch = clock::now();
+      g.rc = lrc;
+      g.state = lrc ? FAILED : LAUNCHED;
+      ++stats_.groups;
+      if (nmsg > stats_.max_messages_in_group) stats_.max_messages_in_group = nmsg;
+      signal();
+    } else {
+      await(lk, [&] { return g.state == LAUNCHED || g.state == FAILED; });
+    }
+
+    int rc = g.state == FAILED ? g.rc : 0;
+    bool redone = false;
+    uint32_t equations = 0;
+    if (rc == 0) {
+      const clock::time_point t0 = g.t_launch;
+      lk.unlock();
+      rc = collect(b, gb, slot, msg, len, gc_round, vote_target, t0, digest32, kind, redone, equations);
+      lk.lock();
+    }
+    stats_.redone_messages += redone ? 1 : 0;
+    stats_.equations += equations;
+    if (--g.refs == 0) {
+      g.state = FREE;
+      signal();
+    }
+    return rc;
+  }
+  // an earlier group is closed or in flight and its members have not all left
+  bool busy_other(const Group& g) const {
+    for (const Group& o : groups_)
+      if (&o != &g && o.state != FREE && o.state != OPEN) return true;
+    return false;
+  }
+
+  // a member's own result: poll its word, fall back to the backend's wait, redo if it asks for it
+  int collect(int b, const GroupBuf& gb, uint32_t slot, const uint8_t* msg, size_t len, uint64_t gc_round,
+              const uint8_t* vote_target, clock::time_point t0, uint8_t* digest32, uint8_t* kind, bool& redone,
+              uint32_t& equations) {
+    uint32_t w = 0;
+    for (uint32_t spins = 0; !((w = __atomic_load_n(gb.results + slot, __ATOMIC_ACQUIRE)) & R_WRITTEN); ++spins) {
+      if ((spins & 255) == 255 && clock::now() - t0 > poll_timeout_) {
+        if (int rc = be_.wait(b)) return rc;
+        w = __atomic_load_n(gb.results + slot, __ATOMIC_ACQUIRE);
+        break;
+      }
+      relax(spins);
+    }
+    if (!(w & R_WRITTEN) || (w & R_REDO)) {   // unwritten after the wait, or "decide me again"
+      redone = true;
+      return be_.redo(msg, len, gc_round, vote_target, digest32, kind);
+    }
+    equations = result_equations(w);
+    if (digest32) std::memcpy(digest32, gb.digests + 32 * (size_t)slot, 32);
+    if (kind) *kind = gb.kinds[slot];
+    return (int)result_code(w);
+  }
+
+  Backend& be_;
+  std::vector<Group> groups_;
+  const uint32_t max_msg_;
+  const uint64_t byte_cap_;
+  const uint32_t max_wait_;
+  const std::chrono::microseconds poll_timeout_;
+  std::mutex mu_;
+  std::condition_variable cv_;
+  std::atomic<uint64_t> epoch_{0};
+  int open_ = -1;
+  uint32_t users_ = 0;
+  bool stopping_ = false;
+  Stats stats_;
+};
+
+}  // namespace sq
+}  // namespace nwc

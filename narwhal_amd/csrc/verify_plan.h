@@ -80,6 +80,10 @@ struct Settings {
   uint64_t msg_chunk = NWC_MSG_CHUNK;     // 0 = one copy, then one pass
   uint64_t sign_wide_max = 256;
   uint32_t verifier_group_eq = NWC_VERIFIER_GROUP_EQ;
+  // nwc_sanitizer_create: wire bytes (4 KiB to 64 MiB, a multiple of 256) and messages (1 to 65,536)
+  // one group holds
+  uint64_t sanitizer_group_bytes = 1u << 20;
+  uint32_t sanitizer_group_msgs = 256;
   // initial values of the run-time knobs (nwc_diag_set)
   uint32_t launch_keys = 1, straus_nq = 12, force_windows = 0, msm_group = 0, msm_adapt = 1;
 
@@ -129,6 +133,9 @@ struct Settings {
     s.sign_wide_max = u64("NWC_SIGN_WIDE_MAX", s.sign_wide_max);
     if (const char* e = lookup("NWC_VERIFIER_GROUP_EQ"))
       s.verifier_group_eq = (uint32_t)std::min<unsigned long>(std::max<unsigned long>(std::strtoul(e, nullptr, 10), 1), 1ul << 16);
+    s.sanitizer_group_bytes =
+        std::min<uint64_t>(std::max<uint64_t>(u64("NWC_SANITIZER_GROUP_BYTES", s.sanitizer_group_bytes), 4096), 64u << 20) / 256 * 256;
+    s.sanitizer_group_msgs = std::min<uint32_t>(std::max<uint32_t>(u32("NWC_SANITIZER_GROUP_MSGS", s.sanitizer_group_msgs), 1), 1u << 16);
     s.launch_keys = u32("NWC_LAUNCH_KEYS", s.launch_keys);
     s.straus_nq = u32("NWC_STRAUS_NQ", s.straus_nq);
     s.force_windows = u32("NWC_FORCE_WINDOWS", s.force_windows);

@@ -25,7 +25,7 @@ from . import _lib
 from .crypto import Digest, PublicKey, SecretKey, Signature, digest_bytes
 
 __all__ = ["DagError", "Authority", "Committee", "Header", "Vote", "Certificate", "sanitize_many",
-           "DAG_ERRORS"]
+           "Sanitizer", "DAG_ERRORS"]
 
 DAG_ERRORS = ["Ok", "InvalidSignature", "InvalidHeaderId", "MalformedHeader", "UnknownAuthority",
               "AuthorityReuse", "CertificateRequiresQuorum", "TooOld", "SerializationError", "UnexpectedVote",
@@ -183,6 +183,70 @@ class Certificate:
     def verify(self, committee: Committee) -> None:
         """Certificate::verify (messages.rs:189-215); raises DagError."""
         _raise(sanitize_many([self.to_bytes()], committee)[0])
+
+
+class Sanitizer:
+    """Concurrent one-message sanitize calls behind shared pipeline launches (nwc_sanitizer):
+    `sanitize` blocks and answers as `sanitize_many` on that message alone, but calls made from
+    several threads at once are packed into groups that one set of launches decides.  `gc_round`
+    and `target` belong to the call.  A group closes at `max_messages` messages (0 = as many as
+    fit), when it is full, or `max_wait_us` after it was opened (0 = never wait for company).  The
+    committee is the one last installed (`Committee.install`).  A context manager; `close()` lets
+    queued requests finish.  `lib`: a loaded library (tests)."""
+
+    STATS = ("groups", "messages", "bytes", "equations", "redone_messages", "bypassed_messages",
+             "max_messages_in_group", "reserved")
+
+    def __init__(self, max_messages: int = 0, max_wait_us: int = 0, lib=None):
+        self._lib = lib if lib is not None else _lib.load()
+        self.handle = self._lib.nwc_sanitizer_create(max_messages, max_wait_us)
+        if not self.handle:
+            raise _lib.DeviceError("nwc_sanitizer_create failed (%d): %s" % (self._lib.nwc_last_error_code(),
+                                                                             self._lib.nwc_last_error().decode()))
+
+    def sanitize(self, wire: bytes, gc_round: int = 0, target: Optional[Header] = None) -> Tuple[int, Digest, int]:
+        """(code, digest, kind) of one wire message: the NWC_DAG_* code (< 0: a device error), the
+        message's digest and its kind (0 header, 1 vote, 2 certificate, 3 other)."""
+        wire = bytes(wire)
+        t = None
+        if target is not None:
+            t = bytes(target.id) + struct.pack("<Q", target.round) + bytes(target.author)
+        dig = ctypes.create_string_buffer(32)
+        kind = ctypes.create_string_buffer(1)
+        code = self._lib.nwc_sanitizer_sanitize(self.handle, _lib.buf(wire) if wire else None, len(wire), gc_round,
+                                                _lib.buf(t) if t else None, dig, kind)
+        return int(code), Digest(dig.raw), kind.raw[0]
+
+    def check(self, wire: bytes, gc_round: int = 0, target: Optional[Header] = None) -> Tuple[Digest, int]:
+        """`sanitize`, raising DagError for a code > 0 and DeviceError for a code < 0; (digest, kind)."""
+        code, dig, kind = self.sanitize(wire, gc_round, target)
+        if code < 0:
+            raise _lib.DeviceError("libnwc error %d: %s" % (code, self._lib.nwc_last_error().decode()))
+        if code != 0:
+            raise DagError(code)
+        return dig, kind
+
+    def stats(self) -> dict:
+        out = (ctypes.c_uint64 * len(self.STATS))()
+        _lib.check(self._lib.nwc_sanitizer_stats(self.handle, out))
+        return {k: int(v) for k, v in zip(self.STATS, out)}
+
+    def close(self) -> None:
+        if self.handle:
+            h, self.handle = self.handle, None
+            _lib.check(self._lib.nwc_sanitizer_destroy(h))
+
+    def __enter__(self) -> "Sanitizer":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001  (interpreter teardown)
+            pass
 
 
 def _raise(err: Optional[DagError]) -> None:

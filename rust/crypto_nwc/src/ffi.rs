@@ -61,6 +61,11 @@ extern "C" {
                                      bad_bitmap: *mut u8) -> c_int;
     pub fn nwc_verifier_stats(verifier: *mut c_void, out: *mut u64) -> c_int;
     pub fn nwc_verifier_destroy(verifier: *mut c_void) -> c_int;
+    pub fn nwc_sanitizer_create(max_messages: u32, max_wait_us: u32) -> *mut c_void;
+    pub fn nwc_sanitizer_sanitize(sanitizer: *mut c_void, msg: *const u8, len: usize, gc_round: u64, vote_target: *const u8,
+                                  digest32: *mut u8, kind: *mut u8) -> c_int;
+    pub fn nwc_sanitizer_stats(sanitizer: *mut c_void, out: *mut u64) -> c_int;
+    pub fn nwc_sanitizer_destroy(sanitizer: *mut c_void) -> c_int;
     pub fn nwc_set_committee(pks: *const u8, n: usize) -> c_int;
     pub fn nwc_cache_stats(committee_keys: *mut u32, auto_keys: *mut u32) -> c_int;
     pub fn nwc_auto_cache_info(capacity: *mut u32, builds: *mut u64, hits: *mut u64) -> c_int;

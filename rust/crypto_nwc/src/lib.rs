@@ -306,3 +306,81 @@ impl Drop for Verifier {
         unsafe { ffi::nwc_verifier_destroy(self.h) };
     }
 }
+
+/// Concurrent wire messages behind shared pipeline launches (`nwc_sanitizer`): the tasks of
+/// `PrimaryReceiverHandler::dispatch` (primary/src/primary.rs:224-240) call one process-wide
+/// `Sanitizer`, each with the bincode `PrimaryMessage` it received; messages that arrive together
+/// share one set of launches and each caller returns when its own verdict is in.  Same codes,
+/// digests and kinds as `nwc_sanitize_messages` on the message alone.  The committee is the one
+/// last given to `nwc_set_committee_config`.
+pub struct Sanitizer {
+    h: *mut std::os::raw::c_void,
+}
+
+unsafe impl Send for Sanitizer {}
+unsafe impl Sync for Sanitizer {}   // every call on a sanitizer may be made from any number of threads
+
+/// Counters of a `Sanitizer` (`nwc_sanitizer_stats_t`).
+#[repr(C)]
+#[derive(Default, Debug, Clone, Copy)]
+pub struct SanitizerStats {
+    pub groups: u64,
+    pub messages: u64,
+    pub bytes: u64,
+    pub equations: u64,
+    pub redone_messages: u64,
+    pub bypassed_messages: u64,
+    pub max_messages_in_group: u64,
+    pub reserved: u64,
+}
+
+/// What `Core::sanitize_*` says about one wire message.
+#[derive(Debug, Clone, Copy, PartialEq, Eq)]
+pub struct Verdict {
+    /// `NWC_DAG_*`: 0 = Ok, otherwise the `DagError` variant.
+    pub code: u32,
+    /// `Header::digest` / `Vote::digest` / `Certificate::digest` of the message.
+    pub digest: [u8; 32],
+    /// 0 header, 1 vote, 2 certificate, 3 anything else.
+    pub kind: u8,
+}
+
+impl Sanitizer {
+    /// A group closes at `max_messages` messages (0 = as many as fit) or `max_wait_us` after it was
+    /// opened (0 = never wait for company).  Panics on a device failure, and before
+    /// `nwc_set_committee_config`.
+    pub fn new(max_messages: u32, max_wait_us: u32) -> Self {
+        init(0);
+        let h = unsafe { ffi::nwc_sanitizer_create(max_messages, max_wait_us) };
+        if h.is_null() {
+            let msg = unsafe { CStr::from_ptr(ffi::nwc_last_error()) };
+            panic!("libnwc sanitizer: {}", msg.to_string_lossy());
+        }
+        Sanitizer { h }
+    }
+
+    /// One wire message under the caller's `gc_round` and, for votes, the current header
+    /// (`id || round (LE) || author`, 72 bytes).  Panics on a device failure.
+    pub fn sanitize(&self, wire: &[u8], gc_round: u64, vote_target: Option<&[u8; 72]>) -> Verdict {
+        let mut v = Verdict { code: 0, digest: [0u8; 32], kind: 3 };
+        let rc = unsafe {
+            ffi::nwc_sanitizer_sanitize(self.h, wire.as_ptr(), wire.len(), gc_round,
+                                        vote_target.map_or(std::ptr::null(), |t| t.as_ptr()), v.digest.as_mut_ptr(), &mut v.kind)
+        };
+        check(rc);
+        v.code = rc as u32;
+        v
+    }
+
+    pub fn stats(&self) -> SanitizerStats {
+        let mut s = SanitizerStats::default();
+        check(unsafe { ffi::nwc_sanitizer_stats(self.h, &mut s as *mut SanitizerStats as *mut u64) });
+        s
+    }
+}
+
+impl Drop for Sanitizer {
+    fn drop(&mut self) {
+        unsafe { ffi::nwc_sanitizer_destroy(self.h) };
+    }
+}
