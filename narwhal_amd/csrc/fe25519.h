@@ -8,7 +8,8 @@
 // beats a saturated 8x32-bit product-scanning multiply, and fe_add/fe_sub are 10 carry-free
 // VOP2 ops instead of a 16-op carry chain.
 //
-// Bounds (the standard analysis for this radix; exercised by tests/test_gpu_parity.py):
+// Bounds (the standard analysis for this radix; tests/test_gpu_prims.py runs every function here at
+// the class maxima on the device, tests/test_prims_host.py holds the group formulas' call sites to them):
 //   "tight"  : |f_i| <= 1.01 * 2^25 (even i) / 1.01 * 2^24 (odd i)     -- fe_mul/fe_sq output
 //   "loose"  : |f_i| <= 1.65 * 2^26 / 1.65 * 2^25                      -- allowed mul/sq input
 // A sum or difference of up to three tight elements is loose.

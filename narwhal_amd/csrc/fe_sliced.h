@@ -13,7 +13,10 @@
 //
 // Bounds are those of fe25519.h (inputs "loose", outputs "tight" + a small carry-in): the
 // wrapped factor 19 goes on g (|19 g| < 2^31), the odd-odd factor 2 on g's odd limbs
-// (|38 g_odd| < 2^31 for |g_odd| <= 1.65 * 2^25), column sums stay below 2^62.
+// (|38 g_odd| < 2^31 for |g_odd| <= 1.65 * 2^25), column sums stay below 2^62.  fes_mul_small is
+// the exception: one carry round, so its limbs are centred + a carry below 2^18 (x 19 on limb 0),
+// past tight but a valid g once a tight element is added (gs_xonly_dbl_n).  tests/test_gpu_prims.py
+// runs these at the class maxima, four different elements per wave.
 #pragma once
 #include "fe25519.h"
 
@@ -84,7 +87,8 @@ FES_DEV fes fes_mul(fes f, fes g) {
   const i32 clo = row_shr<1>((i32)(u32)c) | row_shl<9>((i32)(u32)c19);
   const i32 chi = row_shr<1>((i32)(c >> 32)) | row_shl<9>((i32)(c19 >> 32));
   const i64 h2 = (i64)r + (i64)(((u64)(u32)chi << 32) | (u32)clo);
-  // round 2: carries of at most 2^12 (x 19 into limb 0), limbs centred by removing the bias
+  // round 2: carries of at most 2^12 (x 19 into limb 0; limb 0's own, which took 19 x column 9's
+  // round-1 carry, stays below 2^16 into limb 1), limbs centred by removing the bias
   const i32 c2 = (i32)(h2 >> w);
   const u32 r2 = (u32)h2 & ((1u << w) - 1u);
   const i32 c219 = k == 9 ? c2 * 19 : 0;

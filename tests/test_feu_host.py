@@ -9,6 +9,8 @@ sanitizers linked into the program itself and run as a child process.  Checked h
     2^64, and the result is tight.  Limbs are non-negative, so the maxima are the worst case.
     A new call site with a new pair of classes has to be added to MUL_SITES / SQ_SITES / SUB_SITES;
   * the doubling and the table / Niels additions against oracle/ed25519_ref.py.
+The device build of the same operations (feu_asm.h's v_mad_u64_u32 half) is held to the same operand rows,
+limb for limb against this host build, by tests/test_gpu_prims.py::test_unsigned_field_on_the_device.
 """
 import os
 import random
@@ -135,6 +137,13 @@ def test_field_ops_against_integers(exe, tmp_path):
     ops.tofile(fin)
     run(exe, ["field", fin, fout])
     out = np.fromfile(fout, dtype=np.uint32).reshape(len(ops), 11, 10)
+    check_field_output(ops, tags, out)
+
+
+def check_field_output(ops, tags, out):
+    """The `field` records (feu_host.cpp's layout, 11 x 10 words per operand pair) against integers:
+    values mod p and the tightness of every product.  tests/test_gpu_prims.py applies the same checks to
+    the device build of the same operations."""
     a, b = values(ops[:, :10]), values(ops[:, 10:])
     tags = np.array(tags)
     tight = np.array(TIGHT, dtype=np.int64)
