@@ -107,6 +107,180 @@ FEU_FN geu_p3 geu_p3_neg(const geu_p3& p, bool neg) {
   return r;
 }
 
+// ---- the joint signed radix-4 table of two decoded points, its recoding and its ladder --------
+// The uncached half-size ladder computes c P + d Q (P = +-A, Q = -R) two scalar bits of each per
+// window from ONE table of a P + b Q, a, b in {-2..2}: 12 points up to sign and the identity.
+// Entry index of (a, b): |5 a + b| (0 identity; 1, 2: Q, 2Q; 3..7: P - 2Q .. P + 2Q; 8..12:
+// 2P - 2Q .. 2P + 2Q); the sign of 5 a + b is the sign of the pair, so j = 5 a + b is the joint code.
+// P and Q arrive as decoded (Z = 1, T = X Y, X and T of class 2 T: r or 2p - r), which the
+// builder uses: 2 Z^2 and 2 Z1 Z2 are the constant 2, 2 X Y is 2 T, and adding P or Q to a running
+// point is a Niels addition (3M).  Every formula is the unified one, complete on this curve, so
+// P = +-Q, small-order points and the identity take the same path as any other input.
+// Keeps the instruction scheduler from interleaving two independent chains of field operations
+// (each keeps a point's worth of registers live): the 2-waves-per-SIMD register budget.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GEU_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
+#else
+#define GEU_SCHED_FENCE() ((void)0)
+#endif
+constexpr int JOINT_ENTRIES = 13;
+constexpr int JOINT_WINDOWS_MIN = 66, JOINT_WINDOWS_MAX = 74;
+FEU_FN int geu_joint_code(int a, int b) { return 5 * a + b; }
+
+FEU_FN feu feu_two() { feu r = feu_zero(); r.v[0] = 2; return r; }
+
+// 2 P of a decoded point (dbl-2008-hwcd with Z = 1): B = 2 Z^2 = 2, and E = (X + Y)^2 - X^2 - Y^2 =
+// 2 X Y = 2 T costs no square.  X, T <= 2 T, Y tight.  Out as geu_p2_dbl: X 4 T, Y 2 T, Z 3 T, T tight.
+FEU_FN geu_p1p1 geu_dbl_affine(const geu_p3& p) {
+  geu_p1p1 r;
+  const feu xx = feu_sq(p.X);                  // 2 T
+  const feu yy = feu_sq(p.Y);                  // T
+  r.X = feu_add(p.T, p.T);                     // 4 T
+  r.Y = feu_add(yy, xx);                       // 2 T
+  r.Z = feu_sub<2>(yy, xx);                    // T + 2p - T: 3 T
+  r.T = feu_weak(feu_sub<2>(feu_add(feu_two(), xx), yy));   // 2 + T + 2p - T: carried
+  return r;
+}
+// P + Q (neg: P - Q) of two decoded points: D = 2 Z1 Z2 = 2, and tt = T_P . 2d T_Q is shared by the
+// two (it changes sign with Q).  (pa, pb) = (Y + X, Y - X) of P, (qa, qb) the same of Q, swapped by
+// the caller for -Q: each 3 T; tt tight.  Out: X 3 T, Y 2 T, Z and T <= 3 T (2 + tt is tight: limb 0 of
+// a product is an exact mask, so + 2 stays in T's slack; 2 + 2p - tt <= 2p + 2).
+FEU_FN geu_p1p1 geu_add_affine(const feu& pa, const feu& pb, const feu& qa, const feu& qb, const feu& tt, bool neg) {
+  geu_p1p1 r;
+  const feu pp = feu_mul(pa, qa);              // 3 T x 3 T
+  const feu mm = feu_mul(pb, qb);              // 3 T x 3 T
+  r.X = feu_sub<2>(pp, mm);                    // 3 T
+  r.Y = feu_add(pp, mm);                       // 2 T
+  const feu g = feu_add(feu_two(), tt);        // tight
+  const feu f = feu_sub<2>(feu_two(), tt);     // 2 + 2p - T
+  r.Z = feu_select(g, f, neg);
+  r.T = feu_select(f, g, neg);
+  return r;
+}
+
+// The table: tab(e, entry) stores entry e as (Y+X, Y-X, 2Z, 2dT) with every coordinate <= 3 T
+// (kernels.hip packs it tight), tab.load(e, k) reads coordinate k of a stored entry back, tight.
+// 12S + 69M.  P and Q die after their doublings and their own entries: the loop holds the shared
+// product tt and ONE running point (P + Q, then P - Q) and reads the coordinates of P and Q back
+// from their entries where it needs them, as the ladder's additions do.
+template <class Tab>
+FEU_FN void geu_build_joint(const Tab& tab, const geu_p3& P, const geu_p3& Q) {
+  constexpr int EP = 5, EQ = 1;                // geu_joint_code(1, 0), (0, 1)
+  tab.identity();                              // entry 0: (1, 1, 2, 0)
+  tab(geu_joint_code(2, 0), geu_p3_to_cached(geu_p1p1_to_p3(geu_dbl_affine(P))));
+  GEU_SCHED_FENCE();
+  tab(geu_joint_code(0, 2), geu_p3_to_cached(geu_p1p1_to_p3(geu_dbl_affine(Q))));
+  GEU_SCHED_FENCE();
+  feu tt;
+  {
+    const geu_cached cq = geu_p3_to_cached(Q); // YpX, YmX 3 T, Z2 = 2, T2d tight
+    tab(EQ, cq);
+    tt = feu_mul(P.T, cq.T2d);                 // 2 T x T
+    tab(EP, geu_p3_to_cached(P));
+  }
+#pragma unroll 1
+  for (int b = 1; b >= -1; b -= 2) {
+    const bool neg = b < 0;
+    const int ka = neg ? 1 : 0, kb = neg ? 0 : 1;                                            // b Q: -Q swaps Y + X, Y - X
+    const geu_p3 cur = geu_p1p1_to_p3(geu_add_affine(tab.load(EP, 0), tab.load(EP, 1), tab.load(EQ, ka),
+                                                     tab.load(EQ, kb), tt, neg));           // P + b Q: all tight
+    tab(geu_joint_code(1, b), geu_p3_to_cached(cur));
+    GEU_SCHED_FENCE();
+    // + b Q and + P: Niels additions of an affine point from its entry, (2 T, 3 T) x T and T x T
+    tab(geu_joint_code(1, 2 * b), geu_p3_to_cached(geu_p1p1_to_p3(
+        geu_add_niels(cur, tab.load(EQ, ka), tab.load(EQ, kb), tab.load(EQ, 3), neg))));
+    GEU_SCHED_FENCE();
+    tab(geu_joint_code(2, b), geu_p3_to_cached(geu_p1p1_to_p3(
+        geu_add_niels(cur, tab.load(EP, 0), tab.load(EP, 1), tab.load(EP, 3), false))));
+    GEU_SCHED_FENCE();
+    geu_p2 c2; c2.X = cur.X; c2.Y = cur.Y; c2.Z = cur.Z;
+    tab(geu_joint_code(2, 2 * b), geu_p3_to_cached(geu_p1p1_to_p3(geu_p2_dbl(c2))));
+  }
+}
+
+// Signed radix-4 digits of x < 2^(2W-1) for a wave-uniform W in [66, 74], least significant first:
+// digits 0..W-2 in [-2, 1] by recode16's carry rule (v = two bits + carry; carry = (v + 2) >> 2),
+// digit W-1 in [0, 2] takes the last carry.  Adding 2 to every digit below W-1 in ONE 160-bit
+// addition propagates exactly those carries: with y = x + sum_{i < W-1} 2 . 4^i, digit i is
+// ((y >> 2i) & 3) - 2 and the top digit is y >> 2(W-1).  Returns the top digit (clamped to the
+// table for lanes whose scalars are out of range: their verdict comes from the fallback).
+FEU_FN int geu_recode4(const u32 x[5], int W, u32 y[5]) {
+  const u32 sh = 2u * (u32)(W - 1) - 128u;     // 2 .. 18
+  u64 c = 0;
+#pragma unroll
+  for (int i = 0; i < 5; ++i) {
+    c += (u64)x[i] + (i < 4 ? 0xAAAAAAAAu : (0xAAAAAAAAu & ((1u << sh) - 1u)));
+    y[i] = (u32)c;
+    c >>= 32;
+  }
+  const u32 top = y[4] >> sh;
+  return (int)(top < 2u ? top : 2u);
+}
+// digit w (< W-1) from word w >> 4 of y
+FEU_FN int geu_digit4(u32 word, int w) { return (int)((word >> (2 * (w & 15))) & 3u) - 2; }
+
+// The ladder's first entry as a completed point (2X : 2Y : 2Z : 2Z): X 3 T, Y 2 T, Z = T tight.
+// tab.load(e, k): coordinate k (0 Y+X, 1 Y-X, 2 2Z, 3 2dT) of entry e, tight.
+template <class Tab>
+FEU_FN geu_p1p1 geu_joint_first(const Tab& tab, int e) {
+  const feu ypx = tab.load(e, 0), ymx = tab.load(e, 1);
+  geu_p1p1 r;
+  r.X = feu_sub<2>(ypx, ymx);
+  r.Y = feu_add(ypx, ymx);
+  r.Z = tab.load(e, 2);
+  r.T = r.Z;
+  return r;
+}
+// t + (neg ? -q : q) for q = tab[e]: the entry is read coordinate by coordinate, Y+X and Y-X (swapped
+// for -q, a per-lane address choice) before the extended form is built, 2Z and 2dT after.
+// t: X <= 4 T, Z <= 4 T, T and Y <= 3 T (the output of a doubling or of an addition).
+template <class Tab>
+FEU_FN geu_p1p1 geu_joint_add(const geu_p1p1& t, const Tab& tab, int e, bool neg) {
+  const feu qa = tab.load(e, neg ? 1 : 0);     // tight
+  const feu qb = tab.load(e, neg ? 0 : 1);     // tight
+  const geu_p3 p = geu_p1p1_to_p3(t);          // all tight
+  GEU_SCHED_FENCE();
+  const feu qz = tab.load(e, 2);               // tight
+  const feu qt = tab.load(e, 3);               // tight
+  return geu_add_cached(p, qa, qb, qz, qt, neg);
+}
+// c P + d Q (+ what `base` adds) over W joint windows: per window ONE rolled doubling body run
+// twice and ONE table addition, so the hot loop stays inside the instruction cache; the first
+// window starts from its entry.  dg.c(w), dg.d(w): digit w of |c| and d; the top digits are >= 0.
+// base.fetch(w) runs before window w's doublings, base.add(t, w) after its table addition.
+template <class Tab, class Digits, class Base>
+FEU_FN geu_p2 geu_joint_ladder(const Tab& tab, const Digits& dg, int top_c, int top_d, int W, Base& base) {
+  geu_p1p1 t = geu_joint_first(tab, geu_joint_code(top_c, top_d));
+#pragma unroll 1
+  for (int w = W - 1; w >= 0; --w) {
+    base.fetch(w);
+    if (w != W - 1) {
+#pragma unroll 1
+      for (int k = 0; k < 2; ++k) t = geu_p2_dbl(geu_p1p1_to_p2(t));
+      const int j = geu_joint_code(dg.c(w), dg.d(w));
+      t = geu_joint_add(t, tab, j < 0 ? -j : j, j < 0);
+    }
+    base.add(t, w);
+  }
+  return geu_p1p1_to_p2(t);
+}
+
+// The carries of a packed table coordinate: any f <= 3 T to limbs in [0, 2^26) / [0, 2^25) (limb 1
+// < 2^25 + 2), tight.
+FEU_FN void feu_pack_carry(const feu& f, u32 h[10]) {
+  u32 c = 0;
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const int w = (i & 1) ? 25 : 26;
+    const u32 v = f.v[i] + c;
+    c = v >> w;
+    h[i] = v & ((1u << w) - 1u);
+  }
+  h[0] += 19u * c;                     // c <= 3: h[0] < 2^26 + 57
+  h[1] += h[0] >> 26;
+  h[0] &= (1u << 26) - 1u;
+}
+
 }  // namespace nwc
 
 #if defined(__HIPCC__)
@@ -144,8 +318,10 @@ __device__ __forceinline__ void geu_decompress(const u32 w[8], geu_p3& out, u32 
   const feu check = feu_mul(vv, feu_sq(r));
   const bool correct = feu_is_zero(feu_sub<4>(check, u));     // T + 4p - 3 T: 5 T
   const bool flipped = feu_is_zero(feu_add(check, u));        // 4 T
-  const bool flipped_i = feu_is_zero(feu_add(check, feu_mul(u, FEU_SQRTM1)));   // 3 T x T; 2 T
-  r = feu_select(r, feu_mul(r, FEU_SQRTM1), flipped || flipped_i);
+  // dalek also multiplies r by sqrt(-1) when check == -u sqrt(-1); that case only ever picks a root
+  // for an encoding that does not decode (ok is false either way), so its product and zero test
+  // are left out: the verdict never reads such a point, and its classes below do not change
+  r = feu_select(r, feu_mul(r, FEU_SQRTM1), flipped);
   const bool sign = (w[7] >> 31) & 1;
   // dalek: r := |r| (the non-negative root), then x := -r if the sign bit is set, even when r == 0
   out.X = feu_select(r, feu_neg<2>(r), feu_is_negative(r) != sign);   // 2 T

@@ -464,16 +464,7 @@ __device__ __forceinline__ void fe_pack(const fe& f, uint4& lo, uint4& hi) {
 // The non-negative field's entry (fe_u25519.h): any f <= 3 T, no bias; the same carries and layout.
 __device__ __forceinline__ void feu_pack(const feu& f, uint4& lo, uint4& hi) {
   u32 h[10];
-  u32 c = 0;
-  _Pragma("unroll") for (int i = 0; i < 10; ++i) {
-    const int w = (i & 1) ? 25 : 26;
-    const u32 v = f.v[i] + c;
-    c = v >> w;
-    h[i] = v & ((1u << w) - 1u);
-  }
-  h[0] += 19u * c;                     // c <= 3: h[0] < 2^26 + 57
-  h[1] += h[0] >> 26;
-  h[0] &= (1u << 26) - 1u;
+  feu_pack_carry(f, h);                // ge_u25519.h
   pack_limbs(h, lo, hi);
 }
 // Unpacked limbs are in [0, 2^26) / [0, 2^25 + 2): within the multiplier's loose input bound
@@ -675,6 +666,9 @@ __device__ __forceinline__ ge_p2 double_scalarmult(const LaneTable& tab, u32 kd[
 // The accumulator between operations is kept in completed (p1p1) form `t`: an add converts it to
 // extended (4M) because the addition needs T; a doubling only needs (X:Y:Z) (3M).  So the last
 // add of each window feeds the next window's doublings at 3M instead of 4M.
+// The uncached branch runs the same ladder over 2W joint radix-4 windows from one table of
+// a*PA + b*PR (ge_u25519.h: geu_joint_ladder); the committee-cache branch and the cold kernel keep
+// the radix-16 windows described here.
 constexpr int HALF_WINDOWS_MIN = 33, HALF_WINDOWS_MAX = 37;
 struct Digits16 { u32 w[5]; i32 top; };
 struct Digits256 { u32 w[5]; };
@@ -768,7 +762,7 @@ __device__ __forceinline__ Digits24 recode24(const u32 x[5]) {
 // Digit strings parked in LDS for the ladder (k_verify's 256-thread blocks), so no VGPR holds them
 // across the windows: per thread, word k at p[k * 256] (a wave's access is one conflict-free 256 B
 // row).  Words [0, 6): e_B's low-half radix-2^24 digits, [6, 11): its high half, [11, 16) and
-// [16, 21): the Digits16 strings of |c| and d (the uncached ladder).
+// [16, 21): the radix-4 digit strings of |c| and d (the uncached ladder: geu_recode4's words).
 constexpr int BD_HI = B24_LO_DIGITS, BD_C = BD_HI + B24_HI_DIGITS, BD_D = BD_C + 5;
 constexpr int BASE_DIGIT_WORDS = BD_D + 5;   // 21 words per thread
 struct BaseDigits { i32* p; };
@@ -889,50 +883,27 @@ __device__ __forceinline__ void base_adds(ge_p1p1& t, int nb, i32 d0, i32 d1, ui
 __device__ __forceinline__ feu lt_load_feu(const LaneTable& tab, int e, int k) {
   return feu_unpack(tab.p[e * 8 + 2 * k], tab.p[e * 8 + 2 * k + 1]);
 }
-// tab[j] = j * P for j = 0..8 (tab[0] = identity).  P: X, T <= 2 T, Y, Z tight (geu_decompress, negated or not).
-__device__ __forceinline__ void build_table_u(const LaneTable& tab, const geu_p3& P) {
-  const geu_cached p1 = geu_p3_to_cached(P);   // YpX, YmX 3 T, Z2 2 T, T2d tight: right operands below
-  geu_cached id;
-  id.YpX = feu_one(); id.YmX = feu_one(); id.Z2 = feu_add(feu_one(), feu_one()); id.T2d = feu_zero();
-  tab.store(0, id);
-  tab.store(1, p1);
-  geu_p2 p2; p2.X = P.X; p2.Y = P.Y; p2.Z = P.Z;                 // X 2 T, Y, Z tight
-  geu_p3 pj = geu_p1p1_to_p3(geu_p2_dbl(p2));                    // all tight
-  tab.store(2, geu_p3_to_cached(pj));
-#pragma unroll 1
-  for (int j = 3; j < TAB_ENTRIES; ++j) {
-    pj = geu_p1p1_to_p3(geu_add_cached(pj, p1.YpX, p1.YmX, p1.Z2, p1.T2d, false));
-    tab.store(j, geu_p3_to_cached(pj));
+// The joint table of P = +-A and Q = -R (ge_u25519.h: geu_build_joint): 13 entries of 128 B in the
+// lane's slot (2 * TAB_BYTES_PER_LANE = 2304 B), entry |5 a + b| = a P + b Q.
+struct JointTable {
+  LaneTable t;
+  __device__ __forceinline__ void operator()(int e, const geu_cached& c) const { t.store(e, c); }
+  // Entry 0, the identity (1, 1, 2, 0), as its packed words.  The zero comes out of an opaque move:
+  // as plain constants the words were hoisted out of the tile loop, held through it and spilled.
+  __device__ __forceinline__ void identity() const {
+    u32 z;
+    asm volatile("v_mov_b32 %0, 0" : "=v"(z));
+    const uint4 zero = make_uint4(z, z, z, z), one = make_uint4(z | 1u, z, z, z), two = make_uint4(z | 2u, z, z, z);
+    t.p[0] = one; t.p[1] = zero;
+    t.p[2] = one; t.p[3] = zero;
+    t.p[4] = two; t.p[5] = zero;
+    t.p[6] = zero; t.p[7] = zero;
   }
-}
-// The ladder's first entry as a completed point (2X : 2Y : 2Z : 2Z): X 3 T, Y 2 T, Z = T tight.
-__device__ __forceinline__ geu_p1p1 lt_first_u(const LaneTable& tab, int e) {
-  const feu ypx = lt_load_feu(tab, e, 0), ymx = lt_load_feu(tab, e, 1);
-  geu_p1p1 r;
-  r.X = feu_sub<2>(ypx, ymx);
-  r.Y = feu_add(ypx, ymx);
-  r.Z = lt_load_feu(tab, e, 2);
-  r.T = r.Z;
-  return r;
-}
-// t + (neg ? -q : q) for q = tab[e], as add_lt: the entry is read coordinate by coordinate, Y+X and
-// Y-X (swapped for -q, a per-lane address choice) before the extended form is built, 2Z and 2dT after.
-// t: X <= 4 T, Z <= 4 T, T and Y <= 3 T (the output of a doubling or of an addition).
-__device__ __forceinline__ geu_p1p1 add_lt_u(const geu_p1p1& t, const LaneTable& tab, int e, bool neg) {
-  const feu qa = lt_load_feu(tab, e, neg ? 1 : 0);   // tight
-  const feu qb = lt_load_feu(tab, e, neg ? 0 : 1);   // tight
-  const geu_p3 p = geu_p1p1_to_p3(t);                // all tight
-  __builtin_amdgcn_sched_barrier(0);
-  const feu qz = lt_load_feu(tab, e, 2);             // tight
-  const feu qt = lt_load_feu(tab, e, 3);             // tight
-  return geu_add_cached(p, qa, qb, qz, qt, neg);
-}
-// four doublings of t (t in, t out), (X:Y:Z) only; one rolled doubling body
-__device__ __forceinline__ void ladder_dbl4_u(geu_p1p1& t) {
-  geu_p2 p2 = geu_p1p1_to_p2(t);
-#pragma unroll 1
-  for (int j = 0; j < 3; ++j) { t = geu_p2_dbl(p2); p2 = geu_p1p1_to_p2(t); }
-  t = geu_p2_dbl(p2);
+  __device__ __forceinline__ feu load(int e, int k) const { return lt_load_feu(t, e, k); }
+};
+static_assert(JOINT_ENTRIES * TAB_U4_PER_ENTRY * 16 <= 2 * TAB_BYTES_PER_LANE, "the joint table fits the lane's slot");
+__device__ __forceinline__ void build_joint_table_u(const LaneTable& tab, const geu_p3& P, const geu_p3& Q) {
+  geu_build_joint(JointTable{tab}, P, Q);
 }
 // as base_adds; the T24 entries are signed (fe25519.h) and shared with the other kernels, so they
 // are biased on load: y+x, y-x + 2p (<= 3.01 T), 2dxy + p (<= 1.51 T) -- 30 VOP2 for each of 11 adds
@@ -957,35 +928,47 @@ __device__ __forceinline__ void base_adds_u(geu_p1p1& t, int nb, i32 d0, i32 d1,
   }
 }
 
-__device__ __forceinline__ geu_p2 half_scalarmult(const LaneTable& ta, const LaneTable& tr, Digits16 cd, Digits16 dd,
-                                                  BaseDigits bd, const ge_niels_pad* T24,
-                                                  uint4* stage, int W) {
-  // Code-size discipline: the window body holds ONE doubling and ONE Niels add (rolled loops) and
-  // two cached adds, so the hot loop stays inside the instruction cache.
-  i32 da = cd.top, dr = dd.top;   // top digits are >= 0
-  // No entry is held across the doublings (holding the next window's entries through them, as
-  // rounds 1-2 did, kept 80 VGPRs live and spilled): each is gathered inside its add; the digit
-  // strings are parked in LDS (BaseDigits), so the loop carries only the accumulator and a few
-  // scalars
-  park16(bd, BD_C, cd);
-  park16(bd, BD_D, dd);
-  geu_p1p1 t = lt_first_u(ta, da);
-#pragma unroll 1
-  for (int w = W - 1; w >= 0; --w) {
-    i32 d0 = 0, d1 = 0;
-    // the window's first basepoint entry lands during the doublings; the A/R gathers issued
-    // after it then never wait on the DMA (vmcnt counts in order)
-    const int nb = base_fetch(w, bd, d0, d1, T24, stage);
-    if (w != W - 1) {
-      ladder_dbl4_u(t);
-      da = digit16(bd, BD_C, w, W);
-      t = add_lt_u(t, ta, da < 0 ? -da : da, da < 0);
-      dr = digit16(bd, BD_D, w, W);
-    }
-    t = add_lt_u(t, tr, dr < 0 ? -dr : dr, dr < 0);
-    base_adds_u(t, nb, d0, d1, stage, T24);
+// The radix-4 digit strings of |c| and d (geu_recode4's y words) parked at BD_C / BD_D, and the
+// basepoint term: joint window w is the low half of radix-16 window w / 2, whose basepoint digits
+// are added there (w a multiple of 12).
+struct JointDigits {
+  BaseDigits bd;
+  __device__ __forceinline__ int c(int w) const { return geu_digit4((u32)bd.p[(BD_C + (w >> 4)) * 256], w); }
+  __device__ __forceinline__ int d(int w) const { return geu_digit4((u32)bd.p[(BD_D + (w >> 4)) * 256], w); }
+};
+struct JointBase {
+  BaseDigits bd;
+  const ge_niels_pad* T24;
+  uint4* stage;
+  i32 d0, d1;
+  int nb;
+  // the window's first basepoint entry lands during the doublings; the table gathers issued
+  // after it then never wait on the DMA (vmcnt counts in order)
+  __device__ __forceinline__ void fetch(int w) {
+    d0 = 0; d1 = 0;
+    nb = (w & 1) ? 0 : base_fetch(w >> 1, bd, d0, d1, T24, stage);
   }
-  return geu_p1p1_to_p2(t);
+  __device__ __forceinline__ void add(geu_p1p1& t, int) { base_adds_u(t, nb, d0, d1, stage, T24); }
+};
+__device__ __forceinline__ void park4(BaseDigits bd, int off, const u32 y[5]) {
+  _Pragma("unroll") for (int i = 0; i < 5; ++i) bd.p[(off + i) * 256] = (i32)y[i];
+}
+// Smallest W in [66, 74] with x < 2^(2W-1) for all lanes (bits = bit length per lane, <= 147).
+__device__ __forceinline__ int wave_windows4(int bits) {
+  int W = JOINT_WINDOWS_MIN;
+  _Pragma("unroll") for (int k = JOINT_WINDOWS_MIN; k < JOINT_WINDOWS_MAX; ++k)
+    W += __any(bits > 2 * k - 1) ? 1 : 0;
+  return W;
+}
+
+// Q = eB*B + |c|*P + d*Q' over W joint radix-4 windows (ge_u25519.h: geu_joint_ladder).
+// No entry is held across the doublings (holding the next window's entries through them, as
+// rounds 1-2 did, kept 80 VGPRs live and spilled): each is gathered inside its add; the digit
+// strings are parked in LDS (BaseDigits), so the loop carries only the accumulator and a few scalars.
+__device__ __forceinline__ geu_p2 half_scalarmult(const LaneTable& tab, int c_top, int d_top, BaseDigits bd,
+                                                  const ge_niels_pad* T24, uint4* stage, int W) {
+  JointBase base{bd, T24, stage, 0, 0, 0};
+  return geu_joint_ladder(JointTable{tab}, JointDigits{bd}, c_top, d_top, W, base);
 }
 
 // The same ladder over digit strings already parked in LDS (BD_C, BD_D; top digits passed in).
@@ -1057,6 +1040,10 @@ __device__ __forceinline__ void decompress_one(ge_p3 out[1], const u32* a, u32 y
 }
 
 // k = SHA-512(R || A || M) mod l over the raw input bytes (one block: 96 bytes + padding)
+// PIN: the first round's sums of the initial state (constants the compiler evaluates at run time) stay
+// inside the caller's tile loop; hoisted out of it they are held through the whole loop, and in the
+// uncached half-size kernels, which run at the register limit, spilled.
+template <bool PIN = false>
 __device__ __forceinline__ void challenge(const u32 rw[8], const u32 aw[8], const u32 mw[8], u32 kw[8]) {
   uint64_t w[16];
   _Pragma("unroll") for (int i = 0; i < 4; ++i) {
@@ -1067,6 +1054,7 @@ __device__ __forceinline__ void challenge(const u32 rw[8], const u32 aw[8], cons
   w[12] = 0x8000000000000000ULL; w[13] = 0; w[14] = 0; w[15] = 96 * 8;
   uint64_t st[8];
   sha512_init_state(st);
+  if constexpr (PIN) asm volatile("" : "+s"(st[0]), "+s"(st[4]));
   sha512_compress(st, w);
   u32 hw[16];
   _Pragma("unroll") for (int i = 0; i < 8; ++i) {
@@ -1121,7 +1109,7 @@ __device__ __forceinline__ void prologue_u(PrologueU& p, const u32 mw[8], const 
   decompress_u(&p.R, rw, yr, &okr);
   const bool small = strict && (ycanon_is_small_order(ya) || ycanon_is_small_order(yr));
   p.ok = s_ok && oka && okr && !small;
-  challenge(rw, aw, mw, p.kw);
+  challenge<true>(rw, aw, mw, p.kw);
 }
 
 // Full-length equation: R' = k(-A) + sB == R.
@@ -1208,18 +1196,25 @@ __device__ __forceinline__ bool verify_half(const u32 mw[8], const u32 aw[8], co
   PrologueU p;
   prologue_u(p, mw, aw, sigw, strict);
   const lat::HalfScalars h = lat::reduce(p.kw);
-  const int W = max(wave_windows(h.ok ? h.bits : 0), min(force_w, HALF_WINDOWS_MAX));
+  // joint radix-4 windows; force_w counts radix-16 windows (two of these each)
+  const int W = max(wave_windows4(h.ok ? h.bits : 0), 2 * min(force_w, HALF_WINDOWS_MAX));
   fallback = !h.ok;
   {
     Digits24 el, eh;
     base_digits(h.d, p.sw, el, eh);
     base_digits_park(bd, el, eh);
   }
-  const Digits16 cd = recode16(h.c, W), dd = recode16(h.d, W);
+  int c_top, d_top;
+  {
+    u32 y[5];
+    c_top = geu_recode4(h.c, W, y);
+    park4(bd, BD_C, y);
+    d_top = geu_recode4(h.d, W, y);
+    park4(bd, BD_D, y);
+  }
   // -c A = |c| * (c < 0 ? A : -A);  -d R = d * (-R)
-  build_table_u(ta, geu_p3_neg(p.A, !h.c_neg));
-  build_table_u(tr, geu_p3_neg(p.R, true));
-  const geu_p2 q = half_scalarmult(ta, tr, cd, dd, bd, T24, stage, W);   // X, Y, Z tight
+  build_joint_table_u(ta, geu_p3_neg(p.A, !h.c_neg), geu_p3_neg(p.R, true));
+  const geu_p2 q = half_scalarmult(ta, c_top, d_top, bd, T24, stage, W);   // X, Y, Z tight
   const bool ident = feu_is_zero(q.X) && feu_is_zero(feu_sub<2>(q.Y, q.Z));
   return p.ok && ident && h.ok;
 }
@@ -1310,7 +1305,8 @@ __global__ __launch_bounds__(256, NWC_VERIFY_WAVES_PER_SIMD) void k_verify(Verif
   const LaneTable tr{reinterpret_cast<uint4*>(base + TAB_BYTES_PER_LANE)};
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t bb = (uint64_t)blockIdx.x * blockDim.x; bb < n; bb += stride) {
-    const uint64_t b0 = bb + (threadIdx.x & ~63u);   // this wave's 64 equations
+    // this wave's 64 equations (wave-uniform, so a scalar: as a per-lane value it was held through the loop)
+    const uint64_t b0 = bb + ((u32)__builtin_amdgcn_readfirstlane(threadIdx.x) & ~63u);
     const u32 tile = (u32)(b0 >> 6);
     const uint64_t idx = b0 + lane;
     const bool active = idx < n;
