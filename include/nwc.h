@@ -333,6 +333,22 @@ int nwc_auto_cache_info(uint32_t* capacity, uint64_t* builds, uint64_t* hits);
  * Verdicts never depend on it.  Waits for the device.  Diagnostics only. */
 int nwc_launch_keys_info(uint32_t* held, uint32_t* capacity);
 
+/* Where a precomputed point table of the calling thread's device lives, for tests that audit the
+ * stored entries (tests/test_gpu_tables.py): the device address (0 if the table is not built),
+ * the size of one element in bytes, the number of elements and, for the per-key arrays, the keys
+ * held (elements = keys x elements per key; 0 otherwise).  Names: "base_table" (2 x 129 Niels
+ * entries of 120 bytes), "sign_table" (64 x 8), "base24" (2 x (2^23 + 1) padded entries of 128
+ * bytes), "comb_base" (32 x 129), "comb16" (12 x (2^21 + 1)); "committee_keys" (32-byte keys),
+ * "committee_flags" (32-bit words: 1 decodes, 2 small order, 4 torsion), "committee_tables" (129
+ * entries per key), "committee_comb" (19 x 8,193 padded entries per key); "auto_keys", "auto_flags",
+ * "auto_tables", "auto_comb" (the auto key cache, the same shapes); "launch_keys", "launch_flags",
+ * "launch_comb" (the launch keys; they keep no 129-entry tables).  Read-only: it never allocates or
+ * builds, and returns NWC_ERR_ARG for any other name.  Waits for the device.  The address holds
+ * until the next library call that can build, rebuild, regrow or free the table (any verifying or
+ * signing call, nwc_set_committee, nwc_trim, nwc_shutdown); the memory stays the library's and is
+ * only to be read.  Any out pointer may be NULL.  Diagnostics only, not part of the crate's API. */
+int nwc_diag_table(const char* name, uint64_t* address, uint32_t* elem_bytes, uint64_t* elements, uint32_t* keys);
+
 /* ---- worker batch digests behind a Processor-shaped queue (worker/src/processor.rs:35-55) ----
  * Replaces the Processor's per-batch `Sha512::digest(&batch)[..32]` (:38) for workers that can
  * hand batches over in groups.  A digester owns a drain thread on the calling thread's device

@@ -2123,6 +2123,56 @@ int nwc_launch_keys_info(uint32_t* held, uint32_t* capacity) {
   return 0;
 }
 
+// Where a precomputed table lives on the calling thread's device (tests/test_gpu_tables.py reads the
+// entries through its probe library).  Read-only: never allocates or builds.
+int nwc_diag_table(const char* name, uint64_t* address, uint32_t* elem_bytes, uint64_t* elements, uint32_t* keys) {
+  // the name is judged first, so a wrong one is an argument error with or without a device
+  static const char* const NAMES[] = {"base_table", "sign_table", "base24", "comb_base", "comb16", "committee_keys",
+                                      "committee_flags", "committee_tables", "committee_comb", "auto_keys", "auto_flags",
+                                      "auto_tables", "auto_comb", "launch_keys", "launch_flags", "launch_comb"};
+  if (!name) return set_err(NWC_ERR_ARG, "null table name");
+  if (std::none_of(std::begin(NAMES), std::end(NAMES), [&](const char* s) { return std::strcmp(name, s) == 0; }))
+    return set_err(NWC_ERR_ARG, "unknown table '%.40s'", name);
+  if (int rc = require_init()) return rc;
+  DevCtx& d = *ctx(t_dev < (int)g_devs.size() ? t_dev : 0);
+  std::lock_guard<std::mutex> g(d.mu);
+  HIP_TRY(hipSetDevice(d.hip_id));
+  HIP_TRY(hipDeviceSynchronize());   // builds and regrows run on the device's and on callers' streams
+  uint32_t lk_held = 0;
+  if (d.lk_alloc) HIP_TRY(hipMemcpy(&lk_held, d.lk.state, 4, hipMemcpyDeviceToHost));
+  constexpr uint32_t NIELS = sizeof(nwc::ge_niels), PAD = sizeof(nwc::ge_niels_pad);
+  constexpr uint64_t COMB = nwc::COMB_PER_KEY;
+  struct Row { const char* name; const void* p; uint32_t elem; uint64_t per; int64_t nkeys; };   // nkeys < 0: not per key
+  const Row rows[] = {
+      {"base_table", d.base_table.raw(), NIELS, 2 * 129, -1},
+      {"sign_table", d.sign_table.raw(), NIELS, nwc::SIGN_TABLE_ENTRIES, -1},
+      {"base24", d.base24.raw(), PAD, 2 * (uint64_t)nwc::B24_ENTRIES, -1},
+      {"comb_base", d.comb_base.raw(), PAD, nwc::BaseComb::per, -1},
+      {"comb16", d.comb16.raw(), PAD, nwc::COMB16_TOTAL, -1},
+      {"committee_keys", d.cm_keys.raw(), 32, 1, d.cm_n},
+      {"committee_flags", d.cm_flags.raw(), 4, 1, d.cm_n},
+      {"committee_tables", d.cm_tables.raw(), NIELS, 129, d.cm_n},
+      {"committee_comb", d.cm_comb.raw(), PAD, COMB, d.cm_n},
+      {"auto_keys", d.ak_keys.raw(), 32, 1, d.ak_n},
+      {"auto_flags", d.ak_flags.raw(), 4, 1, d.ak_n},
+      {"auto_tables", d.ak_tables.raw(), NIELS, 129, d.ak_n},
+      {"auto_comb", d.ak_comb.raw(), PAD, COMB, d.ak_n},
+      {"launch_keys", d.lk_alloc ? d.lk_keys.raw() : nullptr, 32, 1, lk_held},
+      {"launch_flags", d.lk_alloc ? d.lk_flags.raw() : nullptr, 4, 1, lk_held},
+      {"launch_comb", d.lk_alloc ? d.lk_comb.raw() : nullptr, PAD, COMB, lk_held},
+  };
+  for (const Row& r : rows) {
+    if (std::strcmp(name, r.name) != 0) continue;
+    const uint64_t n = r.p ? (r.nkeys < 0 ? r.per : r.per * (uint64_t)r.nkeys) : 0;
+    if (address) *address = (uint64_t)reinterpret_cast<uintptr_t>(r.p);
+    if (elem_bytes) *elem_bytes = r.elem;
+    if (elements) *elements = n;
+    if (keys) *keys = r.p && r.nkeys > 0 ? (uint32_t)r.nkeys : 0;
+    return 0;
+  }
+  return set_err(NWC_ERR_ARG, "table '%.40s' has no row", name);   // NAMES and rows[] list the same names
+}
+
 int nwc_auto_cache_info(uint32_t* capacity, uint64_t* builds, uint64_t* hits) {
   if (int rc = require_init()) return rc;
   DevCtx& d = *ctx(t_dev < (int)g_devs.size() ? t_dev : 0);

@@ -1,9 +1,11 @@
 // Probe library for tests/test_gpu_prims.py (tests/prim_probe.py builds and wraps it): one
 // translation unit around the device-only primitives of narwhal_amd/csrc -- the signed field
 // (fe25519.h, fe_asm.h), the limb-sliced field and group (fe_sliced.h, ge_sliced.h), the asm half of
-// the unsigned field (feu_asm.h), the scalars (sc25519.h) and point decoding (ge25519.h,
-// ge_u25519.h).  Test infrastructure: compiled with the library's flags, never linked into it, and
-// kept out of narwhal_amd/csrc so the library's build id does not depend on it.
+// the unsigned field (feu_asm.h), the scalars (sc25519.h), point decoding (ge25519.h,
+// ge_u25519.h) and the per-lane group layer (ge25519.h) -- and, for tests/test_gpu_tables.py, two
+// readers of the stored point tables (a gather and an audit, below).  Test infrastructure: compiled
+// with the library's flags, never linked into it, and kept out of narwhal_amd/csrc so the library's
+// build id does not depend on it.
 //
 // Every entry is  int probe_X(const u32* in, u32* out, u32 n, hipStream_t stream): n records of
 // IN_X words at `in`, n records of OUT_X words at `out` (device pointers), one kernel launch, the HIP
@@ -303,6 +305,125 @@ __global__ void k_geu_decompress(const u32* __restrict__ in, u32* __restrict__ o
   st_dec(out + (size_t)t * DEC, q, ok, yc);
 }
 
+// ---- per-lane group layer (ge25519.h) --------------------------------------------------------
+// in: P (X Y Z T), Q (X Y Z T), q = the affine Niels form of Q (ypx ymx xy2d), 110 limbs.
+// out: 2P through ge_p1p1_to_p3 [40], _to_p2 [30], _to_p3_acc [40], _to_p2_acc [30]; P + Q and P - Q
+// through ge_add_cached [40 each]; P + q and P - q through ge_add_niels [40 each]; ge_p3_neg(P) [40]
+constexpr int IN_GE_OPS = 110, OUT_GE_OPS = 340;
+__device__ __forceinline__ ge_p3 ld_p3(const u32* p) {
+  ge_p3 r;
+  r.X = ld_fe(p); r.Y = ld_fe(p + 10); r.Z = ld_fe(p + 20); r.T = ld_fe(p + 30);
+  return r;
+}
+__device__ __forceinline__ void st_p2(u32* p, const ge_p2& q) { st_fe(p, q.X); st_fe(p + 10, q.Y); st_fe(p + 20, q.Z); }
+__global__ void k_ge_ops(const u32* __restrict__ in, u32* __restrict__ out, u32 n) {
+  const u32 t = blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n) return;
+  const u32* r = in + (size_t)t * IN_GE_OPS;
+  u32* o = out + (size_t)t * OUT_GE_OPS;
+  const ge_p3 P = ld_p3(r), Q = ld_p3(r + 40);
+  ge_niels q;
+  q.ypx = ld_fe(r + 80); q.ymx = ld_fe(r + 90); q.xy2d = ld_fe(r + 100);
+  const ge_p1p1 d = ge_p2_dbl(ge_p3_to_p2(P));
+  st_p3(o, ge_p1p1_to_p3(d));
+  st_p2(o + 40, ge_p1p1_to_p2(d));
+  st_p3(o + 70, ge_p1p1_to_p3_acc(d));
+  st_p2(o + 110, ge_p1p1_to_p2_acc(d));
+  const ge_cached qc = ge_p3_to_cached(Q);
+  st_p3(o + 140, ge_p1p1_to_p3(ge_add_cached(P, qc)));
+  st_p3(o + 180, ge_p1p1_to_p3(ge_add_cached(P, ge_cached_cneg(qc, true))));
+  st_p3(o + 220, ge_p1p1_to_p3(ge_add_niels(P, q)));
+  st_p3(o + 260, ge_p1p1_to_p3(ge_add_niels(P, ge_niels_cneg(q, true))));
+  st_p3(o + 300, ge_p3_neg(P));
+}
+
+// ---- stored point tables (tests/test_gpu_tables.py) -------------------------------------------
+// An entry is an affine Niels point: ypx[10] ymx[10] xy2d[10] signed limbs, 120 bytes, or 128 with
+// two pad words.  The tables are read through addresses the caller vouches for: the wrapper
+// (tests/prim_probe.py) takes them from nwc_diag_table or from a buffer it owns, and checks every
+// index against the element count before it launches.
+// in: address (lo, hi), stride in bytes (120 or 128; 32 / 4 for the key / flag arrays), index.
+// out: the element's words (32 at most), the rest 0
+constexpr int IN_GATHER = 4, OUT_GATHER = 32;
+__global__ void k_table_gather(const u32* __restrict__ in, u32* __restrict__ out, u32 n) {
+  const u32 t = blockIdx.x * BLOCK + threadIdx.x;
+  if (t >= n) return;
+  const u32* r = in + (size_t)t * IN_GATHER;
+  const uint64_t addr = ((uint64_t)r[1] << 32) | r[0];
+  const u32 stride = r[2], words = stride / 4 < 32 ? stride / 4 : 32;
+  const u32* src = reinterpret_cast<const u32*>(addr + (uint64_t)r[3] * stride);
+  u32* o = out + (size_t)t * OUT_GATHER;
+  for (u32 i = 0; i < 32; ++i) o[i] = i < words ? src[i] : 0u;
+}
+
+// The audit: one lane per entry of `windows` windows of `entries` entries each, one flag word per
+// entry.  Entry j of a window claims to be j * (the window's entry 1); entry 1 of window w is the
+// table's element one_offset + w * one_stride.
+//   j = 0: the Niels identity, ypx = ymx = 1 mod p                                        (AUDIT_CHAIN)
+//   j > 0: entry[j] = entry[j - 1] + entry[1] by the affine addition law of -x^2 + y^2 = 1 + d x^2 y^2,
+//          x3 (1 + d x1 x2 y1 y2) = x1 y2 + y1 x2,  y3 (1 - d x1 x2 y1 y2) = y1 y2 + x1 x2,
+//          on X = 2x = ypx - ymx and Y = 2y = ypx + ymx:  X3 (16 + d M) = 8 (X1 Y2 + Y1 X2),
+//          Y3 (16 - d M) = 8 (Y1 Y2 + X1 X2),  M = X1 X2 Y1 Y2                               (AUDIT_CHAIN)
+//   every j: 2 xy2d = d X Y                                                                 (AUDIT_NIELS)
+//            |limb| <= 2 x tight for ypx and ymx, tight for xy2d (the bounds come in the record)  (AUDIT_BOUND)
+//            the pad words of a 128-byte entry are 0                                        (AUDIT_PAD)
+// Only fe_mul, fe_mul_small, fe_add, fe_sub and fe_equal: the group formulas that built the tables
+// do not judge them.  With entries 0 and 1 of every window checked exactly by the host, a window
+// without a flag is proven entry by entry.  Stored limbs of any size are first carried into tight
+// form (fe_mul_small by 1 takes whole 32-bit limbs), so an entry out of bounds still has its value.
+// in (one record for the launch): address (lo, hi), stride, windows, entries, one_offset, one_stride,
+// tight bound of an even limb, of an odd limb.  out: n = windows x entries flag words
+constexpr int IN_AUDIT = 9, OUT_AUDIT = 1;
+constexpr u32 AUDIT_CHAIN = 1, AUDIT_NIELS = 2, AUDIT_BOUND = 4, AUDIT_PAD = 8;
+struct AuditEntry { fe ypx, ymx, xy2d; bool in_bounds, pad_clear; };
+__device__ __forceinline__ AuditEntry audit_load(uint64_t addr, u32 stride, uint64_t idx, u32 tight_even, u32 tight_odd) {
+  const u32* src = reinterpret_cast<const u32*>(addr + idx * stride);
+  AuditEntry e;
+  e.in_bounds = true;
+  fe raw[3];
+  _Pragma("unroll") for (int k = 0; k < 3; ++k) {
+    raw[k] = ld_fe(src + 10 * k);
+    _Pragma("unroll") for (int i = 0; i < 10; ++i) {
+      const int64_t bound = (int64_t)((i & 1) ? tight_odd : tight_even) * (k < 2 ? 2 : 1);
+      const int64_t v = raw[k].v[i];
+      e.in_bounds = e.in_bounds && v <= bound && v >= -bound;
+    }
+  }
+  e.ypx = fe_mul_small(raw[0], 1);
+  e.ymx = fe_mul_small(raw[1], 1);
+  e.xy2d = fe_mul_small(raw[2], 1);
+  e.pad_clear = true;
+  for (u32 i = 30; i < stride / 4; ++i) e.pad_clear = e.pad_clear && src[i] == 0u;
+  return e;
+}
+__global__ void k_table_audit(const u32* __restrict__ in, u32* __restrict__ out, u32 n) {
+  const u32 t = blockIdx.x * BLOCK + threadIdx.x;
+  const uint64_t addr = ((uint64_t)in[1] << 32) | in[0];
+  const u32 stride = in[2], windows = in[3], entries = in[4], one_offset = in[5], one_stride = in[6];
+  if (t >= n || (uint64_t)t >= (uint64_t)windows * entries) return;
+  const u32 w = t / entries, j = t % entries;
+  const AuditEntry cur = audit_load(addr, stride, t, in[7], in[8]);
+  u32 flags = (cur.in_bounds ? 0u : AUDIT_BOUND) | (cur.pad_clear ? 0u : AUDIT_PAD);
+  const fe X3 = fe_sub(cur.ypx, cur.ymx), Y3 = fe_add(cur.ypx, cur.ymx);
+  if (!fe_equal(fe_mul_small(cur.xy2d, 2), fe_mul(fe_mul(X3, Y3), FE_D))) flags |= AUDIT_NIELS;
+  if (j == 0) {
+    if (!fe_equal(cur.ypx, fe_one()) || !fe_equal(cur.ymx, fe_one())) flags |= AUDIT_CHAIN;
+  } else {
+    const AuditEntry prev = audit_load(addr, stride, (uint64_t)t - 1, in[7], in[8]);
+    const AuditEntry one = audit_load(addr, stride, (uint64_t)one_offset + (uint64_t)w * one_stride, in[7], in[8]);
+    const fe X1 = fe_sub(prev.ypx, prev.ymx), Y1 = fe_add(prev.ypx, prev.ymx);
+    const fe X2 = fe_sub(one.ypx, one.ymx), Y2 = fe_add(one.ypx, one.ymx);
+    const fe a = fe_mul(X1, Y2), b = fe_mul(Y1, X2), c = fe_mul(Y1, Y2), e = fe_mul(X1, X2);
+    const fe dm = fe_mul(fe_mul(a, b), FE_D);
+    fe sixteen = fe_zero();
+    sixteen.v[0] = 16;
+    const bool x_ok = fe_equal(fe_mul(X3, fe_add(sixteen, dm)), fe_mul_small(fe_add(a, b), 8));
+    const bool y_ok = fe_equal(fe_mul(Y3, fe_sub(sixteen, dm)), fe_mul_small(fe_add(c, e), 8));
+    if (!x_ok || !y_ok) flags |= AUDIT_CHAIN;
+  }
+  out[t] = flags;
+}
+
 template <class K>
 int launch(K kernel, u32 per_block, const u32* in, u32* out, u32 n, hipStream_t stream) {
   if (n == 0) return (int)hipSuccess;
@@ -332,6 +453,10 @@ PROBE(probe_sc_recode, k_sc_recode, BLOCK)
 PROBE(probe_decompress1, k_decompress1, BLOCK)
 PROBE(probe_decompress2, k_decompress2, BLOCK)
 PROBE(probe_geu_decompress, k_geu_decompress, BLOCK)
+PROBE(probe_ge_ops, k_ge_ops, BLOCK)
+PROBE(probe_table_gather, k_table_gather, BLOCK)
+// one parameter record at `in`, n flag words at `out` (n = windows x entries)
+PROBE(probe_table_audit, k_table_audit, BLOCK)
 
 // words per record (in, out) of an entry, so the wrapper's table is checked against this file
 extern "C" int probe_record_words(const char* name, int* in_words, int* out_words) {
@@ -343,6 +468,8 @@ extern "C" int probe_record_words(const char* name, int* in_words, int* out_word
       {"probe_sc_reduce", IN_SC_REDUCE, OUT_SC_REDUCE}, {"probe_sc_lt_l", IN_SC_LT, OUT_SC_LT},
       {"probe_sc_recode", IN_SC_RECODE, OUT_SC_RECODE}, {"probe_decompress1", 8, DEC},
       {"probe_decompress2", 16, 2 * DEC},            {"probe_geu_decompress", 8, DEC},
+      {"probe_ge_ops", IN_GE_OPS, OUT_GE_OPS},       {"probe_table_gather", IN_GATHER, OUT_GATHER},
+      {"probe_table_audit", IN_AUDIT, OUT_AUDIT},
   };
   for (const auto& e : t) {
     const char *a = e.n, *b = name;

@@ -38,6 +38,8 @@ ENTRIES = {
     "probe_fes_ops": (21, 80), "probe_fes_pow": (10, 16), "probe_gs": (80, 324), "probe_feu_field": (20, 110),
     "probe_sc_reduce": (16, 8), "probe_sc_lt_l": (8, 1), "probe_sc_recode": (8, 104),
     "probe_decompress1": (8, 50), "probe_decompress2": (16, 100), "probe_geu_decompress": (8, 50),
+    "probe_ge_ops": (110, 340), "probe_table_gather": (4, 32),
+    "probe_table_audit": (9, 1),   # one parameter record per launch, one flag word per entry (audit_table)
 }
 # records one 256-lane block holds: a lane, a 16-lane row or a wave per record
 PER_BLOCK = {name: 256 for name in ENTRIES}
@@ -125,6 +127,7 @@ def run(name: str, records: np.ndarray) -> np.ndarray:
     """One launch of entry `name` over (n, in_words) records of 32-bit words; (n, out_words) uint32 back."""
     import torch
     lib = load()
+    assert name != "probe_table_audit", "one parameter record per launch: use audit_table()"
     wi, wo = ENTRIES[name]
     rec = np.ascontiguousarray(records)
     assert rec.dtype.itemsize == 4 and rec.ndim == 2 and rec.shape[1] == wi, (name, rec.dtype, rec.shape)
@@ -160,6 +163,87 @@ def ragged(records: np.ndarray, name: str) -> np.ndarray:
     """Records with the first one repeated at the end where the count would fill the last wave / block."""
     unit = 64 if PER_BLOCK[name] == 256 else 4
     return records if len(records) % unit else np.concatenate([records, records[:1]])
+
+
+# ---- stored tables ----------------------------------------------------------------------------
+AUDIT_CHAIN, AUDIT_NIELS, AUDIT_BOUND, AUDIT_PAD = 1, 2, 4, 8
+
+
+class Table:
+    """A table of affine Niels entries in device memory: `elements` entries of `stride` bytes (120, or
+    128 with two pad words) at `address`.  The probe reads what it is told to, so every reader below
+    checks its indices against `elements` first; `owner` keeps a test-owned tensor alive."""
+
+    def __init__(self, address: int, stride: int, elements: int, owner=None):
+        assert stride in (120, 128) and address % 4 == 0 and elements >= 0
+        self.address, self.stride, self.elements, self.owner = int(address), int(stride), int(elements), owner
+
+    def part(self, first: int, count: int) -> "Table":
+        assert 0 <= first and first + count <= self.elements
+        return Table(self.address + first * self.stride, self.stride, count, self.owner)
+
+
+def library_table(name: str):
+    """nwc_diag_table of the calling thread's device: (Table or None if not built, keys held)."""
+    from narwhal_amd import _lib
+    lib = _lib.load()
+    addr, elem, count, keys = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_uint64(), ctypes.c_uint32()
+    _lib.check(lib.nwc_diag_table(name.encode(), ctypes.byref(addr), ctypes.byref(elem), ctypes.byref(count),
+                                  ctypes.byref(keys)))
+    if addr.value == 0:
+        assert count.value == 0 and keys.value == 0, name
+        return None, 0
+    if elem.value in (120, 128):
+        return Table(addr.value, elem.value, count.value), keys.value
+    return (addr.value, elem.value, count.value), keys.value
+
+
+def read_array(array) -> np.ndarray:
+    """A key or flag array of library_table() -- (address, element bytes, elements) with 32-byte keys
+    or 4-byte flag words -- through the gather entry: (elements, element bytes / 4) uint32 words."""
+    address, elem, count = array
+    assert elem in (4, 32) and address % 4 == 0 and count > 0
+    rec = np.empty((count, 4), dtype=np.uint32)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = address & 0xFFFFFFFF, address >> 32, elem, np.arange(count)
+    return run("probe_table_gather", rec)[:, :elem // 4]
+
+
+def gather(table: Table, indices) -> np.ndarray:
+    """Entries `indices` of a table: (n, 32) uint32 words (30 limbs, then the pad words or zeros)."""
+    idx = np.asarray(indices, dtype=np.int64).reshape(-1)
+    assert idx.size and (idx >= 0).all() and (idx < table.elements).all(), "index outside the table"
+    rec = np.empty((idx.size, 4), dtype=np.uint32)
+    rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = table.address & 0xFFFFFFFF, table.address >> 32, table.stride, idx
+    return run("probe_table_gather", rec)
+
+
+def audit_table(table: Table, windows: int, entries: int, one_offset: int = 1, one_stride: int = None):
+    """probe_table_audit over windows x entries entries: (indices, flag words) of the flagged entries."""
+    import torch
+    lib = load()
+    one_stride = entries if one_stride is None else one_stride
+    n = windows * entries
+    assert 0 < n <= table.elements and n < 1 << 32 and entries >= 2
+    assert 0 <= one_offset and one_offset + (windows - 1) * one_stride < table.elements
+    par = np.array([table.address & 0xFFFFFFFF, table.address >> 32, table.stride, windows, entries, one_offset,
+                    one_stride, int(TIGHT[0]), int(TIGHT[1])], dtype=np.uint32)
+    din = torch.from_numpy(par.view(np.int32).copy()).cuda()
+    dout = torch.full((n + 1,), 0x5A5A5A5A, dtype=torch.int32, device="cuda")
+    rc = lib.probe_table_audit(din.data_ptr(), dout.data_ptr(), n, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    assert int(dout[n]) == 0x5A5A5A5A, "probe_table_audit wrote past its last entry"
+    bad = torch.nonzero(dout[:n]).reshape(-1)
+    return bad.cpu().numpy().astype(np.int64), dout[:n][bad].cpu().numpy().view(np.uint32)
+
+
+def device_copy(words: np.ndarray) -> Table:
+    """A test-owned device copy of (n, 32) entry words as a table of 128-byte entries."""
+    import torch
+    words = np.ascontiguousarray(words, dtype=np.uint32)
+    assert words.ndim == 2 and words.shape[1] == 32
+    t = torch.from_numpy(words.view(np.int32).copy()).cuda()
+    return Table(t.data_ptr(), 128, len(words), owner=t)
 
 
 LANE_COUNTS = (1, 63, 64, 65, 257)
@@ -316,6 +400,42 @@ def check_points(recs: np.ndarray, expect, bounds=None, what: str = "") -> None:
             limbs = recs[:, 10 * k:10 * k + 10]
             over = ((limbs > np.asarray(b)) | (limbs < -np.asarray(b))).any(axis=1)
             assert not over.any(), "%s: coordinate %d out of bound at rows %s" % (what, k, _first(over))
+
+
+def check_p2(recs: np.ndarray, expect, bounds=None, what: str = "") -> None:
+    """Projective points (N, 30 signed limbs: X Y Z) against affine points, as check_points without T."""
+    recs = np.asarray(recs, dtype=np.int64)
+    assert recs.shape == (len(expect), 30), (what, recs.shape)
+    for i, (rec, want) in enumerate(zip(recs, expect)):
+        X, Y, Z = (int(x) % P for x in values(rec.reshape(3, 10)))
+        assert Z != 0, "%s: Z = 0 at row %d" % (what, i)
+        zi = pow(Z, P - 2, P)
+        assert (X * zi % P, Y * zi % P) == (want[0] % P, want[1] % P), "%s: wrong point at row %d" % (what, i)
+    if bounds is not None:
+        for k, b in enumerate(bounds):
+            over = (np.abs(recs[:, 10 * k:10 * k + 10]) > np.asarray(b)).any(axis=1)
+            assert not over.any(), "%s: coordinate %d out of bound at rows %s" % (what, k, _first(over))
+
+
+def niels_limbs(point, form: int, rng) -> list:
+    """The affine Niels form (ypx, ymx, xy2d) of a point as 30 signed limbs, in the classes a table entry
+    comes in: form 0 as ge_p3_to_niels and the comb builders store it (ypx, ymx the limb-wise sum and
+    difference of the tight limbs of y and x: up to 2 x tight), form 1 carried (every element tight,
+    a packed entry), form 2 with ypx and ymx at the edge of 2 x tight (a tight element with every
+    limb at +- its maximum, plus the tight remainder).  xy2d is tight in every form."""
+    x, y = point
+    cx, cy = np.array(centred_limbs(x)), np.array(centred_limbs(y))
+    if form == 0:
+        ypx, ymx = cy + cx, cy - cx
+    elif form == 1:
+        ypx, ymx = np.array(centred_limbs(y + x)), np.array(centred_limbs(y - x))
+    else:
+        out = []
+        for v in (y + x, y - x):
+            a = TIGHT * np.array([rng.choice((-1, 1)) for _ in range(10)])
+            out.append(a + np.array(centred_limbs(v - int(values(a[None, :])[0]))))
+        ypx, ymx = out
+    return [int(v) for v in np.concatenate([ypx, ymx, centred_limbs(2 * ref.D * x * y)])]
 
 
 DECODE_TIGHT = (TIGHT, TIGHT, TIGHT, TIGHT)                    # ge_decompress*: every coordinate tight
@@ -490,6 +610,26 @@ def ext_limbs(point, z: int):
     """(X : Y : Z : T) of an affine point scaled by z, as 40 tight signed limbs."""
     x, y = point
     return centred_limbs(x * z) + centred_limbs(y * z) + centred_limbs(z) + centred_limbs(x * y % P * z)
+
+
+def ext_limbs_at_maxima(point, which: int, rng):
+    """(X : Y : Z : T) of an affine point, 40 tight signed limbs, with coordinate `which` (0 X, 1 Y, 2 Z,
+    3 T) at +- the tight maximum in every limb (a random sign pattern): the scale z is chosen so that
+    the coordinate has that value, which its limbs then state as they are.  Falls back to Z where the
+    point's coordinate is zero (no scale reaches a non-zero value)."""
+    x, y = point
+    factor = (x, y, 1, x * y % P)[which] % P
+    if factor == 0:
+        which, factor = 2, 1
+    for _ in range(8):
+        edge = TIGHT * np.array([rng.choice((-1, 1)) for _ in range(10)])
+        z = int(values(edge[None, :])[0]) % P * pow(factor, P - 2, P) % P
+        if z:
+            break
+    out = ext_limbs(point, z)
+    assert (int(values(np.array(out[10 * which:10 * which + 10])[None, :])[0]) - int(values(edge[None, :])[0])) % P == 0
+    out[10 * which:10 * which + 10] = [int(v) for v in edge]
+    return out
 
 
 def reduce_inputs(seed: int, n_uniform: int = 20000):

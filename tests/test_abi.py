@@ -66,6 +66,27 @@ def test_diag_set_rejects_bad_knobs_without_a_device():
     assert lib.nwc_diag_set(b"straus_nq", 12) == 0 and lib.nwc_diag_set(b"force_windows", 0) == 0
 
 
+def test_diag_table_judges_its_name_before_anything_else():
+    """nwc_diag_table: an unknown or missing name is an argument error with or without a device, and
+    leaves the out parameters alone; a known name without nwc_init is NWC_ERR_NOT_INIT, never an address."""
+    from narwhal_amd import _lib
+    lib = _lib.load(init=False)
+    addr, elem, count, keys = ctypes.c_uint64(77), ctypes.c_uint32(77), ctypes.c_uint64(77), ctypes.c_uint32(77)
+    outs = (ctypes.byref(addr), ctypes.byref(elem), ctypes.byref(count), ctypes.byref(keys))
+    for name in (b"no_such_table", b"", b"base_table ", b"BASE24", b"launch_tables", b"committee", None):
+        assert lib.nwc_diag_table(name, *outs) == _lib.NWC_ERR_ARG, name
+        assert lib.nwc_last_error_code() == _lib.NWC_ERR_ARG
+    assert b"table" in lib.nwc_last_error()
+    assert (addr.value, elem.value, count.value, keys.value) == (77, 77, 77, 77)
+    if lib.nwc_device_count() == 0:
+        for name in (b"base_table", b"sign_table", b"base24", b"comb_base", b"comb16", b"committee_keys",
+                     b"committee_flags", b"committee_tables", b"committee_comb", b"auto_keys", b"auto_flags",
+                     b"auto_tables", b"auto_comb", b"launch_keys", b"launch_flags", b"launch_comb"):
+            assert lib.nwc_diag_table(name, *outs) == _lib.NWC_ERR_NOT_INIT, name
+            assert lib.nwc_diag_table(name, None, None, None, None) == _lib.NWC_ERR_NOT_INIT, name
+        assert (addr.value, elem.value, count.value, keys.value) == (77, 77, 77, 77)
+
+
 def test_gfx950_code_object_present():
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "-n", LIB], capture_output=True, text=True).stdout
     blob = open(LIB, "rb").read()

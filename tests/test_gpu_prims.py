@@ -198,6 +198,54 @@ def test_sliced_group():
     report("sliced group", len(rec), len(rec))
 
 
+# ---- per-lane group layer ---------------------------------------------------------------------
+def test_group_ops():
+    """ge25519.h one operation at a time, one point pair per lane: ge_p2_dbl through the four p1p1
+    conversions, ge_add_cached and ge_add_niels with and without the conditional negation, ge_p3_neg.
+    The pairs are all of group_points() x group_points() (the identity, the small-order points,
+    multiples of B, mixed-order points; P = Q on the diagonal) and (P, -P) for every P, under random
+    Z; P and Q come tight -- in 64 further records with one coordinate each at +- the tight maximum in
+    every limb -- and the Niels operand in the three classes a table entry comes in (as built, carried,
+    at the edge of 2 x tight).  Every output coordinate is a product: tight."""
+    import random
+    rng = random.Random(41)
+    pts = pp.group_points()
+    pairs = [(p, q) for p in pts for q in pts] + [(p, ref.pt_neg(p)) for p in pts]
+    assert sum(p == q for p, q in pairs) >= len(pts) and sum(ref.pt_add(p, q) == (0, 1) for p, q in pairs) >= len(pts)
+    rows = [pp.ext_limbs(p, rng.randrange(1, P)) + pp.ext_limbs(q, rng.randrange(1, P)) + pp.niels_limbs(q, i % 3, rng)
+            for i, (p, q) in enumerate(pairs)]
+    # the tight class at its edge: one coordinate of P and one of Q at +- the tight maximum in every limb
+    # (the scale Z is chosen for it), every coordinate in turn, on every kind of point
+    edge = [(pts[(5 * i) % len(pts)], pts[(7 * i + 3) % len(pts)]) for i in range(64)]
+    rows += [pp.ext_limbs_at_maxima(p, i % 4, rng) + pp.ext_limbs_at_maxima(q, (i // 4) % 4, rng) + pp.niels_limbs(q, i % 3, rng)
+             for i, (p, q) in enumerate(edge)]
+    pairs += edge
+    rec = i32(rows)
+    lim = pp.signed(rec)
+    at_max = (np.abs(lim[len(rows) - 64:, :80].reshape(-1, 10)) == pp.TIGHT).all(axis=1).reshape(64, 8)
+    assert (at_max.sum(axis=1) >= 2).all() and at_max[:, :4].any(axis=0).all() and at_max[:, 4:].any(axis=0).all()
+    assert (np.abs(lim[:, :80].reshape(-1, 10)) <= pp.TIGHT).all()
+    assert (np.abs(lim[:, 80:100].reshape(-1, 10)) <= 2 * pp.TIGHT).all() and (np.abs(lim[:, 100:110]) <= pp.TIGHT).all()
+    assert (np.abs(lim[2::3, 80:100].reshape(-1, 10)).max(axis=0) > 1.5 * pp.TIGHT).all()   # form 2 goes well past tight in every limb
+    rec = pp.ragged(rec, "probe_ge_ops")
+    pairs = pairs + pairs[:len(rec) - len(pairs)]
+    out = pp.signed(pp.run_whole_and_ragged("probe_ge_ops", rec, pp.LANE_COUNTS))
+    t4, t3 = (pp.TIGHT,) * 4, (pp.TIGHT,) * 3
+    dbl = [ref.pt_add(p, p) for p, _ in pairs]
+    add = [ref.pt_add(p, q) for p, q in pairs]
+    sub = [ref.pt_add(p, ref.pt_neg(q)) for p, q in pairs]
+    pp.check_points(out[:, 0:40], dbl, t4, "ge_p1p1_to_p3(ge_p2_dbl)")
+    pp.check_p2(out[:, 40:70], dbl, t3, "ge_p1p1_to_p2(ge_p2_dbl)")
+    pp.check_points(out[:, 70:110], dbl, t4, "ge_p1p1_to_p3_acc(ge_p2_dbl)")
+    pp.check_p2(out[:, 110:140], dbl, t3, "ge_p1p1_to_p2_acc(ge_p2_dbl)")
+    pp.check_points(out[:, 140:180], add, t4, "ge_add_cached")
+    pp.check_points(out[:, 180:220], sub, t4, "ge_add_cached of ge_cached_cneg")
+    pp.check_points(out[:, 220:260], add, t4, "ge_add_niels")
+    pp.check_points(out[:, 260:300], sub, t4, "ge_add_niels of ge_niels_cneg")
+    pp.check_points(out[:, 300:340], [ref.pt_neg(p) for p, _ in pairs], t4, "ge_p3_neg")
+    report("per-lane group layer", len(rec), len(rec))
+
+
 # ---- unsigned field, device build -------------------------------------------------------------
 @pytest.fixture(scope="module")
 def feu_plain_exe():
