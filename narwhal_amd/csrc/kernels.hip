@@ -656,8 +656,9 @@ __device__ __forceinline__ ge_p2 double_scalarmult(const LaneTable& tab, u32 kd[
 // W is wave-uniform: the smallest W in [33, 37] with |c|, d < 2^(4W-1) for every lane of the
 // wave (max(|c|, d) has 127-128 bits typically; ~9 % of waves hold a lane of 132+ bits and run
 // 34-35 windows, and only |c| or d >= 2^147 -- never seen in 10^6 samples -- leaves the
-// half-size path).  The basepoint scalar eB = d s mod l is split at 2^132 into two 9-digit
-// radix-2^16 strings added at the windows w = 32, 28, ..., 0 from tables in HBM.
+// half-size path).  The basepoint scalar eB = d s mod l is split at 2^141 into signed radix-2^24
+// digits, six of the low half and five of the high half (recode24, base_digits), added at the
+// windows w = 30, 24, ..., 0 from the base24 tables in HBM (one digit at w = 30, two below).
 // Digit streams are packed so the next digit is always in the top nibble/byte of word 4 and is
 // consumed by shifting the 160-bit string left:
 //   Digits16  {w[5], top}: signed radix-16 digits of x < 2^(4W-1): digits 0..W-2 in [-8, 7] as
@@ -969,27 +970,6 @@ __device__ __forceinline__ geu_p2 half_scalarmult(const LaneTable& tab, int c_to
                                                   const ge_niels_pad* T24, uint4* stage, int W) {
   JointBase base{bd, T24, stage, 0, 0, 0};
   return geu_joint_ladder(JointTable{tab}, JointDigits{bd}, c_top, d_top, W, base);
-}
-
-// The same ladder over digit strings already parked in LDS (BD_C, BD_D; top digits passed in).
-__device__ __forceinline__ ge_p2 half_scalarmult_parked(const LaneTable& ta, const LaneTable& tr, i32 c_top, i32 d_top,
-                                                        BaseDigits bd, const ge_niels_pad* T24, uint4* stage, int W) {
-  i32 da = c_top, dr = d_top;   // top digits are >= 0
-  ge_p1p1 t = ge_cached_to_p1p1(lt_first(ta, da));
-#pragma unroll 1
-  for (int w = W - 1; w >= 0; --w) {
-    i32 d0 = 0, d1 = 0;
-    const int nb = base_fetch(w, bd, d0, d1, T24, stage);
-    if (w != W - 1) {
-      ladder_dbl4(t);
-      da = digit16(bd, BD_C, w, W);
-      t = add_lt(t, ta, da < 0 ? -da : da, da < 0);
-      dr = digit16(bd, BD_D, w, W);
-    }
-    t = add_lt(t, tr, dr < 0 ? -dr : dr, dr < 0);
-    base_adds(t, nb, d0, d1, stage, T24);
-  }
-  return ge_p1p1_to_p2(t);
 }
 
 // Half-size ladder with a cached key: Q = eB*B + c'*(-A) + d*(-R) where the A term uses the key's

@@ -82,6 +82,9 @@ def probe_up_to_date(path: str = OUT) -> bool:
 def build_probe(out: str = OUT, force: bool = False) -> str:
     """hipcc with the library's own flags; rebuilt when the probe source, a csrc header or a flag changed."""
     from narwhal_amd import build as nb
+    if out == OUT:   # the in-tree build (__graft_entry__.build()) carries the half-size probe with it
+        from tests import half_probe
+        half_probe.build_probe(force=force)
     if not force and probe_up_to_date(out):
         return out
     os.makedirs(os.path.dirname(out), exist_ok=True)

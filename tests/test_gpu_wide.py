@@ -8,6 +8,7 @@ is placed in a wave of its own with 63 ordinary triples, a quarter of all triple
 the verdicts are compared with the oracle (dalek verify_strict restated).  Natural 136+-bit lanes
 (W >= 35) are rarer than 1 in 10^6, so W = 34..37 are also forced on ordinary batches through the
 nwc_diag_set("force_windows") test hook (extra top windows carry zero digits; the verdicts must not change).
+The widths this module cannot reach (real digits in windows 35..37) are fed directly in tests/test_gpu_half.py.
 """
 import ctypes
 import hashlib
