@@ -189,6 +189,16 @@ int nwc_signer_sign_many(void* signer, const uint8_t* msgs32, size_t n, uint8_t*
 /* Device-resident: d_msgs (16-byte aligned) holds digest i at msg_stride * i, msg_stride = 32, or
  * 0 for one digest signed n times; d_sigs n x 64 B.  Asynchronous on `stream`.  n < 2^31. */
 int nwc_dev_sign(void* signer, const void* d_msgs, uint64_t msg_stride, uint64_t n, void* d_sigs, void* stream);
+/* Vote::new (primary/src/messages.rs:115-129): sig = sign(SHA-512(id || round LE || origin)[..32]),
+ * the digest computed on the device in the same launch as the signature, for a header the caller
+ * has already accepted.  id and origin are only hashed (any 32 bytes).  Conventions, chunking,
+ * polling and the choice of kernel ("sign_path", NWC_SIGN_WIDE_MAX) as nwc_signer_sign_many. */
+int nwc_signer_vote(void* signer, const uint8_t id32[32], uint64_t round, const uint8_t origin32[32], uint8_t sig[64]);
+int nwc_signer_vote_many(void* signer, const uint8_t* ids32, const uint64_t* rounds, const uint8_t* origins32,
+                         size_t n, uint8_t* sigs);
+/* device-resident: d_ids, d_origins 16-byte aligned, d_rounds 8-byte, d_sigs 4-byte; asynchronous on stream */
+int nwc_dev_vote(void* signer, const void* d_ids, const void* d_rounds, const void* d_origins, uint64_t n,
+                 void* d_sigs, void* stream);
 /* Overwrites the key record with zeros (a memset on the signer's device stream, waited for), then
  * frees it; waits for the device first, so launches of nwc_dev_sign still in flight finish.  No
  * call on the signer may start after destroy.  nwc_shutdown does the same to signers still alive,
@@ -301,6 +311,30 @@ int nwc_sanitizer_sanitize(void* sanitizer, const uint8_t* msg, size_t len, uint
  * sound) and redone_messages (messages decided again by nwc_sanitize_messages: the result word
  * asked for it or was still unwritten after the stream had been waited for) when a caller leaves. */
 int nwc_sanitizer_stats(void* sanitizer, uint64_t* out);
+/* Core::process_header's next step in the same flight (primary/src/core.rs:202-217 -> Vote::new,
+ * messages.rs:115-129).  As nwc_sanitizer_sanitize; additionally, when the message is a header and
+ * its code is NWC_DAG_OK, vote_sig64 receives Vote::new(header, signer's key).signature and
+ * *voted = 1; otherwise *voted = 0 and vote_sig64 is zeroed (on an error < 0 too).  signer must live
+ * on the sanitizer's device (NWC_ERR_ARG otherwise); vote_sig64 and voted must not be NULL.
+ *
+ * A group in which at least one request carries a signer gets one more launch, shared by all of
+ * its headers; groups without such requests run exactly the launches of nwc_sanitizer_sanitize.
+ * Requests with and without a signer, and with different signers, may share a group.
+ *
+ * Two things that are not obvious:
+ *   - The library is stateless about voting.  Core's last_voted check (at most one vote per origin
+ *     and round, core.rs:206-212) stays the caller's duty; a signature that Core then decides not
+ *     to send is simply dropped.  Ed25519 signing is deterministic, so an unused signature leaks
+ *     nothing that a used one would not.
+ *   - A vote is signed only AFTER the header's code is Ok (the result word of its slot, or the
+ *     batch entry's code for a message that was redone or bypassed), never speculatively on
+ *     unverified wire bytes.
+ * The signer may not be destroyed while a call that carries it is in progress. */
+int nwc_sanitizer_sanitize_vote(void* sanitizer, void* signer, const uint8_t* msg, size_t len, uint64_t gc_round,
+                                const uint8_t* vote_target, uint8_t digest32[32], uint8_t* kind,
+                                uint8_t vote_sig64[64], int32_t* voted);
+/* votes signed inside a group flight / by the one-message fallback.  Either pointer may be NULL. */
+int nwc_sanitizer_vote_stats(void* sanitizer, uint64_t* in_flight, uint64_t* alone);
 int nwc_sanitizer_destroy(void* sanitizer);
 
 /* Committee key cache (config/src/lib.rs:154-156 Committee).  Optional: verdicts never

@@ -55,6 +55,10 @@ _SIGS = {
     "nwc_signer_sign_many": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, ctypes.c_size_t, _c_u8p]),
     "nwc_dev_sign": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
                                     ctypes.c_void_p, ctypes.c_void_p]),
+    "nwc_signer_vote": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, ctypes.c_uint64, _c_u8p, _c_u8p]),
+    "nwc_signer_vote_many": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, ctypes.c_void_p, _c_u8p, ctypes.c_size_t, _c_u8p]),
+    "nwc_dev_vote": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64,
+                                    ctypes.c_void_p, ctypes.c_void_p]),
     "nwc_signer_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "nwc_verifier_create": (ctypes.c_void_p, [ctypes.c_uint32, ctypes.c_uint32]),
     "nwc_verifier_verify_strict": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, _c_u8p, _c_u8p]),
@@ -65,6 +69,10 @@ _SIGS = {
     "nwc_sanitizer_sanitize": (ctypes.c_int, [ctypes.c_void_p, _c_u8p, ctypes.c_size_t, ctypes.c_uint64, _c_u8p, _c_u8p,
                                               _c_u8p]),
     "nwc_sanitizer_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "nwc_sanitizer_sanitize_vote": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                                   _c_u8p, _c_u8p, _c_u8p, _c_u8p, ctypes.POINTER(ctypes.c_int32)]),
+    "nwc_sanitizer_vote_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_uint64)]),
     "nwc_sanitizer_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "nwc_set_committee": (ctypes.c_int, [_c_u8p, ctypes.c_size_t]),
     "nwc_cache_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

@@ -268,6 +268,14 @@ def keypair_from_seed(seed: bytes) -> Tuple[PublicKey, SecretKey]:
     return PublicKey(out.raw[32:]), SecretKey(out.raw)
 
 
+def _vote_field(x) -> bytes:
+    """The 32 bytes of a Digest, a PublicKey or a bytes-like (a vote's id or origin)."""
+    b = x.to_vec() if isinstance(x, Digest) else bytes(x)
+    if len(b) != 32:
+        raise ValueError("a vote's id and origin must be 32 bytes")
+    return b
+
+
 class Signer:
     """A registered signing key (nwc_signer): the key is expanded once into device memory and every
     signature after that is one launch of a sign kernel.  A context manager; `close()` (or leaving
@@ -308,6 +316,29 @@ class Signer:
             return []
         out = ctypes.create_string_buffer(64 * n)
         _lib.check(self._lib.nwc_signer_sign_many(self.handle, _lib.buf(b"".join(ds)), n, out))
+        raw = out.raw
+        return [Signature.from_bytes(raw[64 * i:64 * i + 64]) for i in range(n)]
+
+    def vote(self, id, round: int, origin) -> "Signature":
+        """`Vote::new(header, ..)`'s signature (messages.rs:115-129) for a header the caller has
+        accepted: the signature of SHA-512(id || round LE || origin)[..32], digest and signature
+        in one launch (nwc_signer_vote)."""
+        i, o = _vote_field(id), _vote_field(origin)
+        out = ctypes.create_string_buffer(64)
+        _lib.check(self._lib.nwc_signer_vote(self.handle, _lib.buf(i), int(round), _lib.buf(o), out))
+        return Signature.from_bytes(out.raw)
+
+    def vote_many(self, votes: Sequence) -> list:
+        """One launch for all of `votes`, a sequence of (id, round, origin) (nwc_signer_vote_many)."""
+        votes = list(votes)
+        n = len(votes)
+        if n == 0:
+            return []
+        ids = b"".join(_vote_field(v[0]) for v in votes)
+        origins = b"".join(_vote_field(v[2]) for v in votes)
+        rounds = (ctypes.c_uint64 * n)(*[int(v[1]) for v in votes])
+        out = ctypes.create_string_buffer(64 * n)
+        _lib.check(self._lib.nwc_signer_vote_many(self.handle, _lib.buf(ids), rounds, _lib.buf(origins), n, out))
         raw = out.raw
         return [Signature.from_bytes(raw[64 * i:64 * i + 64]) for i in range(n)]
 

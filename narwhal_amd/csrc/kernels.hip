@@ -2623,6 +2623,8 @@ __global__ __launch_bounds__(256) void k_keygen_sign(const uint8_t* __restrict__
 #include "msm.h"
 #include "resolve.h"
 #include "sign.h"
+#include "messages.h"
+#include "vote.h"
 namespace nwc {
 
 // Seeds / messages of the synthetic workloads (SURVEY.md §8(d) cfg 2):

@@ -138,12 +138,14 @@ inline MsgArena msg_arena(size_t m, uint64_t total, uint64_t vt, bool ysplit, bo
 // max_msgs + v.
 //   SanGroupBuf: one pinned group buffer -- the wire bytes with 16 bytes of readable padding, the
 //     per-message starts, lengths, gc_rounds and vote targets (80 B), and on the way back the result
-//     words, digests and kinds.
+//     words, digests and kinds; then what a vote request adds (nwc_sanitizer_sanitize_vote): the
+//     device address of the signer's key record (8 B, 0 = no vote asked), the vote's signature
+//     (64 B) and its "written" byte.
 //   SanScratch: the HBM scratch of the handle (one group runs at a time on the device's stream).
 //     eq_msg is followed by cdig (one digest array of 2 x max_msgs); `counters` is the vote-slot
 //     allocator and the list count.
 struct SanGroupBuf {
-  size_t data, starts, lens, gc_rounds, targets, results, digests, kinds;
+  size_t data, starts, lens, gc_rounds, targets, results, digests, kinds, vote_keys, vote_sigs, vote_flags;
   size_t bytes;
 };
 inline SanGroupBuf san_group_buf(size_t max_msgs, uint64_t byte_cap) {
@@ -157,6 +159,9 @@ inline SanGroupBuf san_group_buf(size_t max_msgs, uint64_t byte_cap) {
   a.results = w.take(4 * max_msgs);
   a.digests = w.take(32 * max_msgs);
   a.kinds = w.take(max_msgs);
+  a.vote_keys = w.take(8 * max_msgs);
+  a.vote_sigs = w.take(64 * max_msgs);
+  a.vote_flags = w.take(max_msgs);
   a.bytes = w.off;
   return a;
 }

@@ -17,6 +17,14 @@
 // when max_wait_us have passed since it was opened, or -- max_wait_us == 0 -- as soon as no earlier
 // group is in flight: a lone caller launches at once, and under load a group is whatever arrived
 // while the previous one was busy.
+//
+// A request may ask for Vote::new on its header (submit's vote_key: the device address of a signer's
+// key record).  Every member writes its slot's key -- 0 when it asks for none, so that a key left by
+// the buffer's previous group is never signed for -- and clears its slot's vote flag byte; the
+// backend's launch signs, inside the same flight, for the slots that carry a key and whose word
+// says Ok + header.  Such a member polls its flag byte after its result word.  A vote the flight did
+// not deliver (flag unwritten, message redone or bypassed) comes from Backend::vote_alone, asked
+// only once the message's code is known to be Ok and its kind a header: never speculatively.
 #pragma once
 
 #include <atomic>
@@ -52,7 +60,13 @@ struct GroupBuf {
   uint32_t* results = nullptr;    // per message: the result word
   uint8_t* digests = nullptr;     // per message, 32 B: written before the result word
   uint8_t* kinds = nullptr;       // per message: written before the result word
+  uint64_t* vote_keys = nullptr;  // per message: the vote request's key (0 = none); null: a backend without votes
+  uint8_t* vote_sigs = nullptr;   // per message, 64 B: written before the vote flag
+  uint8_t* vote_flags = nullptr;  // per message: bit 7 = the vote's signature is in
 };
+
+constexpr uint8_t VOTE_WRITTEN = 0x80;
+constexpr uint32_t KIND_HEADER = 0;   // PrimaryMessage::Header, as the kinds array and the kind output carry it
 
 struct Backend {
   virtual ~Backend() = default;
@@ -68,11 +82,19 @@ struct Backend {
   // A message that does not go through a group (larger than one, or the caller asked): as redo.
   virtual int bypass(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32,
                      uint8_t* kind) = 0;
+  // Vote::new for one message that was decided Ok and is a header (id32: its digest), outside a
+  // group: 0 and the signature under vote_key in sig64, or an error < 0.  A backend without votes
+  // keeps this default.
+  virtual int vote_alone(const uint8_t* /*msg*/, size_t /*len*/, const uint8_t* /*id32*/, uint64_t /*vote_key*/,
+                         uint8_t* /*sig64*/) {
+    return NWC_ERR_ARG;
+  }
 };
 
 struct Stats {
   uint64_t groups = 0, messages = 0, bytes = 0, equations = 0, redone_messages = 0, bypassed_messages = 0,
            max_messages_in_group = 0, reserved = 0;
+  uint64_t votes_in_flight = 0, votes_alone = 0;   // votes signed inside a group flight / by vote_alone
 };
 
 class Queue {
@@ -94,20 +116,35 @@ class Queue {
   // Returns the message's code >= 0 (digest32 and kind, both nullable, filled), or an error < 0
   // (the group's launch failed, the device reported an error, or the queue was stopped:
   // NWC_ERR_NOT_INIT).  direct: hand the message to Backend::bypass whatever its size.
+  // vote_key != 0 asks for Vote::new under that key when the message is a header and its code is
+  // Ok: vote_sig (64 bytes) then holds the signature and *voted is 1; otherwise -- an error
+  // included -- *voted is 0 and vote_sig is zeroed.  Both are required with a key.
   int submit(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32, uint8_t* kind,
-             bool direct = false) {
+             bool direct = false, uint64_t vote_key = 0, uint8_t* vote_sig = nullptr, int* voted = nullptr) {
+    if (vote_sig) std::memset(vote_sig, 0, 64);
+    if (voted) *voted = 0;
+    if (vote_key && (!vote_sig || !voted)) return NWC_ERR_ARG;
     std::unique_lock<std::mutex> lk(mu_);
     if (stopping_) return NWC_ERR_NOT_INIT;
     ++users_;
     int rc;
+    Vote v{vote_key, vote_sig, voted};
     if (direct || len > byte_cap_) {
       ++stats_.bypassed_messages;
       lk.unlock();
-      rc = be_.bypass(msg, len, gc_round, vote_target, digest32, kind);
+      // (the vote needs the digest and the kind whether or not the caller asked for them)
+      uint8_t dig[32], kd = 0xFF;
+      rc = be_.bypass(msg, len, gc_round, vote_target, vote_key ? dig : digest32, vote_key ? &kd : kind);
+      if (vote_key && rc >= 0 && (rc = vote_outside(msg, len, rc, dig, kd, v)) >= 0) {   // (an error touches no output)
+        if (digest32) std::memcpy(digest32, dig, 32);
+        if (kind) *kind = kd;
+      }
       lk.lock();
     } else {
-      rc = grouped(lk, msg, len, gc_round, vote_target, digest32, kind);
+      rc = grouped(lk, msg, len, gc_round, vote_target, digest32, kind, v);
     }
+    stats_.votes_in_flight += v.in_flight ? 1 : 0;
+    stats_.votes_alone += v.alone ? 1 : 0;
     if (--users_ == 0) signal();
     return rc;
   }
@@ -128,6 +165,25 @@ class Queue {
 
  private:
   enum State { FREE, OPEN, CLOSED, LAUNCHED, FAILED };
+  // one request's vote: what it asked for and which route delivered it
+  struct Vote {
+    uint64_t key;
+    uint8_t* sig;
+    int* voted;
+    bool in_flight = false, alone = false;
+  };
+  // a message decided outside a group (redo, bypass) or whose flag stayed unwritten: the vote comes
+  // from the backend, and only for an Ok header.  Returns the code, or vote_alone's error.
+  int vote_outside(const uint8_t* msg, size_t len, int code, const uint8_t* id32, uint8_t kind, Vote& v) {
+    if (!v.key || code != 0 || kind != KIND_HEADER) return code;
+    if (int rc = be_.vote_alone(msg, len, id32, v.key, v.sig)) {
+      std::memset(v.sig, 0, 64);
+      return rc < 0 ? rc : NWC_ERR_DEVICE;
+    }
+    *v.voted = 1;
+    v.alone = true;
+    return code;
+  }
   struct Group {
     State state = FREE;
     uint32_t nmsg = 0;
@@ -186,7 +242,7 @@ class Queue {
   }
 
   int grouped(std::unique_lock<std::mutex>& lk, const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target,
-              uint8_t* digest32, uint8_t* kind) {
+              uint8_t* digest32, uint8_t* kind, Vote& v) {
     // a place in the open group, or a free buffer to open the next one in
     int b = -1;
     bool leader = false;
@@ -231,6 +287,15 @@ class Queue {
     std::memset(t + TARGET_FLAG_AT, 0, TARGET_STRIDE - TARGET_FLAG_AT);
     t[TARGET_FLAG_AT] = vote_target ? 1 : 0;
     __atomic_store_n(gb.results + slot, 0u, __ATOMIC_RELAXED);
+    if (gb.vote_keys) {
+      // The previous group's vote launch may still be running when its last member has left (a
+      // member that asked for nothing leaves with its result word).  It reads a slot's key and then
+      // its result word, so the cleared word must be out before a new key is: a late block that
+      // sees this key then finds no "written" bit and leaves.  (A key of 0 needs no such order.)
+      __atomic_store_n(gb.vote_flags + slot, (uint8_t)0, __ATOMIC_RELAXED);
+      if (v.key) __atomic_thread_fence(__ATOMIC_SEQ_CST);
+      __atomic_store_n(gb.vote_keys + slot, v.key, __ATOMIC_RELEASE);   // 0 included: the previous group's key goes
+    }
     lk.lock();
     if (--g.copying == 0) signal();
 
@@ -269,7 +334,7 @@ class Queue {
     if (rc == 0) {
       const clock::time_point t0 = g.t_launch;
       lk.unlock();
-      rc = collect(b, gb, slot, msg, len, gc_round, vote_target, t0, digest32, kind, redone, equations);
+      rc = collect(b, gb, slot, msg, len, gc_round, vote_target, t0, digest32, kind, redone, equations, v);
       lk.lock();
     }
     stats_.redone_messages += redone ? 1 : 0;
@@ -290,7 +355,7 @@ class Queue {
   // a member's own result: poll its word, fall back to the backend's wait, redo if it asks for it
   int collect(int b, const GroupBuf& gb, uint32_t slot, const uint8_t* msg, size_t len, uint64_t gc_round,
               const uint8_t* vote_target, clock::time_point t0, uint8_t* digest32, uint8_t* kind, bool& redone,
-              uint32_t& equations) {
+              uint32_t& equations, Vote& v) {
     uint32_t w = 0;
     for (uint32_t spins = 0; !((w = __atomic_load_n(gb.results + slot, __ATOMIC_ACQUIRE)) & R_WRITTEN); ++spins) {
       if ((spins & 255) == 255 && clock::now() - t0 > poll_timeout_) {
@@ -302,12 +367,42 @@ class Queue {
     }
     if (!(w & R_WRITTEN) || (w & R_REDO)) {   // unwritten after the wait, or "decide me again"
       redone = true;
-      return be_.redo(msg, len, gc_round, vote_target, digest32, kind);
+      if (!v.key) return be_.redo(msg, len, gc_round, vote_target, digest32, kind);
+      uint8_t dig[32], kd = 0xFF;
+      int rc = be_.redo(msg, len, gc_round, vote_target, dig, &kd);
+      if (rc < 0 || (rc = vote_outside(msg, len, rc, dig, kd, v)) < 0) return rc;
+      if (digest32) std::memcpy(digest32, dig, 32);
+      if (kind) *kind = kd;
+      return rc;
     }
     equations = result_equations(w);
+    const int code = (int)result_code(w);
+    const uint8_t kd = gb.kinds[slot];
+    if (v.key && code == 0 && kd == KIND_HEADER) {
+      // the flight signs after the result words: poll the slot's flag under the same time limit
+      bool in = false;
+      if (gb.vote_flags) {
+        auto written = [&] { return (__atomic_load_n(gb.vote_flags + slot, __ATOMIC_ACQUIRE) & VOTE_WRITTEN) != 0; };
+        for (uint32_t spins = 0; !(in = written()); ++spins) {
+          if ((spins & 255) == 255 && clock::now() - t0 > poll_timeout_) {
+            if (int rc = be_.wait(b)) return rc;
+            in = written();
+            break;
+          }
+          relax(spins);
+        }
+      }
+      if (in) {
+        std::memcpy(v.sig, gb.vote_sigs + 64 * (size_t)slot, 64);
+        *v.voted = 1;
+        v.in_flight = true;
+      } else if (int rc = vote_outside(msg, len, code, gb.digests + 32 * (size_t)slot, kd, v); rc < 0) {
+        return rc;
+      }
+    }
     if (digest32) std::memcpy(digest32, gb.digests + 32 * (size_t)slot, 32);
-    if (kind) *kind = gb.kinds[slot];
-    return (int)result_code(w);
+    if (kind) *kind = kd;
+    return code;
   }
 
   Backend& be_;

@@ -12,6 +12,15 @@
 // latency kernel's preconditions do not hold (the committee cache is the configured committee and
 // has its combs; NWC_COLD and NWC_VERIFY_PATH at their defaults), is handed to
 // nwc_sanitize_messages; so is a message whose result word asks for it (redo).
+//
+// Vote::new in the flight (nwc_sanitizer_sanitize_vote; vote.h): a request may carry a signer.  Its
+// slot of the group buffer then holds the device address of the signer's key record, and a group
+// with at least one such slot gets a fourth launch, k_vote_group, behind k_finalize_group: one wave
+// per message, which signs where the slot has a key and the result word says Ok + header.  Groups
+// without vote requests run the three launches above and nothing else.  A vote the flight did not
+// deliver (the message was redone or bypassed, or the flag stayed unwritten) is signed by
+// vote_alone: the header's author string and round cross the device's pinned stage and k_vote_wire
+// decodes them as the parse does -- the host has no base64 decoder.
 #include "sanitize_queue.h"
 
 namespace {
@@ -39,6 +48,9 @@ struct Sanitizer final : nwc::sq::Backend {
     g.results = reinterpret_cast<uint32_t*>(p + gl.results);
     g.digests = p + gl.digests;
     g.kinds = p + gl.kinds;
+    g.vote_keys = reinterpret_cast<uint64_t*>(p + gl.vote_keys);
+    g.vote_sigs = p + gl.vote_sigs;
+    g.vote_flags = p + gl.vote_flags;
     return g;
   }
   nwc::sq::GroupBuf buffer(int b) override { return view(host[b]->get()); }
@@ -116,6 +128,17 @@ struct Sanitizer final : nwc::sq::Backend {
                        knobs().sanitizer_redo_every.load(), counters, counters + 1);
     HIP_TRY(hipGetLastError());
     counters_dirty = false;
+    // Vote::new for the slots that carry a key, once their result words are out (stream order)
+    bool votes = false;
+    for (uint32_t i = 0; i < nmsg && !votes; ++i) votes = h.vote_keys[i] != 0;
+    if (votes) {
+      if (int rc = ensure_sign_table(dc)) return rc;
+      hipLaunchKernelGGL(nwc::k_vote_group, dim3(nmsg), dim3(64), 0, s, (const nwc::ge_niels*)dc.sign_table,
+                         nwc::GroupVotes{g.vote_keys, g.vote_sigs, g.vote_flags}, (const uint32_t*)g.results,
+                         (const uint32_t*)a.rec, (const uint8_t*)a.digests, (const uint8_t*)a.eq_pk, a.data,
+                         (const uint64_t*)g.starts, (const uint32_t*)g.lens, nmsg);
+      HIP_TRY(hipGetLastError());
+    }
     return 0;
   }
 
@@ -141,6 +164,42 @@ struct Sanitizer final : nwc::sq::Backend {
   int bypass(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32,
              uint8_t* kind) override {
     return alone(msg, len, gc_round, vote_target, digest32, kind);
+  }
+
+  // Vote::new for one header the batch entry has accepted.  Only the bytes the vote needs cross
+  // the stage: the variant, the author string and the round (the first 20 + L bytes, L the
+  // string's length at byte 4).
+  int vote_alone(const uint8_t* msg, size_t len, const uint8_t* id32, uint64_t vote_key, uint8_t* sig64) override {
+    DevCtx* dp = d.load();
+    if (!dp) return set_err(NWC_ERR_NOT_INIT, "the sanitizer's device context was shut down");
+    DevCtx& dc = *dp;
+    uint64_t L = 0;
+    if (len >= 12) std::memcpy(&L, msg + 4, 8);
+    if (len < 20 || L > len - 20) return set_err(NWC_ERR_ARG, "vote: the message holds no header author and round");
+    const size_t need = 20 + (size_t)L, io = nwc::plan::align256(need + 16), so = io + 256, fo = so + 256;
+    if (fo + 256 > NWC_PINNED_STAGE_MAX) return set_err(NWC_ERR_ARG, "vote: the author string does not fit the pinned stage");
+    std::lock_guard<std::mutex> lk(dc.mu);
+    HIP_TRY(hipSetDevice(dc.hip_id));
+    if (int rc = ensure_sign_table(dc)) return rc;
+    if (int rc = dc.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
+    uint8_t* const hs = dc.pinned;
+    uint8_t* const ds = dc.pinned.dev();
+    std::memcpy(hs, msg, need);
+    std::memset(hs + need, 0, io - need);
+    std::memcpy(hs + io, id32, 32);
+    std::memset(hs + so, 0, 64);
+    hs[fo] = 0;
+    hipLaunchKernelGGL(nwc::k_vote_wire, dim3(1), dim3(64), 0, dc.stream, reinterpret_cast<const nwc::SignKey*>(vote_key),
+                       (const nwc::ge_niels*)dc.sign_table, (const uint8_t*)ds, (uint64_t)need, (const uint8_t*)(ds + io), ds + so,
+                       ds + fo);
+    HIP_TRY(hipGetLastError());
+    if (!settings().spin_wait || !nwc::plan::poll_written(hs + fo, 1, std::chrono::milliseconds(200))) {
+      HIP_TRY(hipStreamSynchronize(dc.stream));
+      if (!nwc::plan::poll_written(hs + fo, 1, std::chrono::microseconds(0)))
+        return set_err(NWC_ERR_DEVICE, "vote kernel left the signature unwritten");
+    }
+    std::memcpy(sig64, hs + so, 64);
+    return 0;
   }
 
   // caller holds the context's mu (the handles leave its set)
@@ -246,6 +305,36 @@ int nwc_sanitizer_sanitize(void* sanitizer, const uint8_t* msg, size_t len, uint
   if (rc == NWC_ERR_NOT_INIT && t_code != NWC_ERR_NOT_INIT)
     return set_err(rc, "the sanitizer was destroyed or its device context shut down");
   return rc;
+}
+
+int nwc_sanitizer_sanitize_vote(void* sanitizer, void* signer, const uint8_t* msg, size_t len, uint64_t gc_round,
+                                const uint8_t* vote_target, uint8_t digest32[32], uint8_t* kind, uint8_t vote_sig64[64],
+                                int32_t* voted) {
+  if (!sanitizer) return set_err(NWC_ERR_ARG, "null sanitizer");
+  if (!vote_sig64 || !voted) return set_err(NWC_ERR_ARG, "null vote output");
+  std::memset(vote_sig64, 0, 64);
+  *voted = 0;
+  if (len && !msg) return set_err(NWC_ERR_ARG, "null message");
+  SIGNER_PROLOGUE(signer);
+  Sanitizer& v = *static_cast<Sanitizer*>(sanitizer);
+  DevCtx* const vd = v.d.load();
+  if (!vd) return set_err(NWC_ERR_NOT_INIT, "the sanitizer was destroyed or its device context shut down");
+  if (vd != sg.d) return set_err(NWC_ERR_ARG, "the signer lives on another device than the sanitizer");
+  t_code = 0;
+  const int rc = v.q->submit(msg, len, gc_round, vote_target, digest32, kind, !Sanitizer::groupable(),
+                             (uint64_t)reinterpret_cast<uintptr_t>(sg.key), vote_sig64, voted);
+  if (rc == NWC_ERR_NOT_INIT && t_code != NWC_ERR_NOT_INIT)
+    return set_err(rc, "the sanitizer was destroyed or its device context shut down");
+  return rc;
+}
+
+int nwc_sanitizer_vote_stats(void* sanitizer, uint64_t* in_flight, uint64_t* alone) {
+  if (!sanitizer) return set_err(NWC_ERR_ARG, "null sanitizer");
+  if (int rc = require_init()) return rc;
+  const nwc::sq::Stats s = static_cast<Sanitizer*>(sanitizer)->q->stats();
+  if (in_flight) *in_flight = s.votes_in_flight;
+  if (alone) *alone = s.votes_alone;
+  return 0;
 }
 
 int nwc_sanitizer_stats(void* sanitizer, uint64_t* out) {

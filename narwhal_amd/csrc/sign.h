@@ -3,8 +3,9 @@
 //
 //   k_build_sign_table  the signer's basepoint table, built on the device (no embedded constants)
 //   k_sign_expand       SecretKey -> key record (a mod l, prefix, A), once per signer
-//   k_sign              throughput: one signature per lane, table in LDS
-//   k_sign_wide         latency: one wave per signature, one window per lane
+//   k_sign              throughput: one signature per lane, table in LDS (body: sign_lane)
+//   k_sign_wide         latency: one wave per signature, one window per lane (body: sign_wave)
+// The vote kernels of vote.h run the same two bodies on Vote::digest.
 //
 // Table: signed radix-16, doubling-free.  SIGN_TABLE[8 w + (j - 1)] = j * 16^w * B for the 64
 // windows w and j = 1..8, affine Niels (120 B): 64 x 8 x 120 B = 61,440 B.  A scalar < 2^253 recodes
@@ -203,39 +204,47 @@ __global__ __launch_bounds__(64) void k_sign_expand(const uint8_t* __restrict__ 
   }
 }
 
-// Throughput kernel: lane i signs digest i (msgs + stride * i, stride 32 or 0).
-__global__ __launch_bounds__(256) void k_sign(const SignKey* __restrict__ key, const ge_niels* __restrict__ table,
-                                              const uint8_t* __restrict__ msgs, uint64_t stride, uint64_t n,
-                                              uint8_t* __restrict__ sigs, uint8_t* __restrict__ flags) {
-  __shared__ ge_niels sT[SIGN_TABLE_ENTRIES];
-  for (int i = threadIdx.x; i < SIGN_TABLE_ENTRIES * 30; i += blockDim.x)
-    reinterpret_cast<i32*>(sT)[i] = reinterpret_cast<const i32*>(table)[i];
-  __syncthreads();
-  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  u32 m[8];
-  load_words8(msgs + stride * i, m);
+// One lane's signature of the digest m: nonce, fixed-base multiplication over the table T (LDS in
+// k_sign and k_vote), response, store to sigs + 64 i (and flags + i, when there are flags).  The
+// body of k_sign; k_vote (vote.h) runs it on Vote::digest.
+FE_DEV void sign_lane(const SignKey* key, const ge_niels* T, const u32 m[8], uint8_t* sigs, uint8_t* flags, uint64_t i) {
   u32 r[8];
   sign_nonce(key, m, r);
   u32 R[8];
-  ge_p3_compress(sign_base_mult(r, sT), R);
+  ge_p3_compress(sign_base_mult(r, T), R);
   u32 s[8];
   sign_response(key, R, m, r, s);
   sign_store(sigs + 64 * i, R, s, flags ? flags + i : nullptr);
 }
 
-// Latency kernel: block (one wave) i signs digest i.  Every lane derives r; lane w takes window
-// w's entry (all 8 candidates read, masked); the 64 points are summed by a 6-level butterfly, after
-// which every lane holds R; the inversion of Z runs limb-sliced (fe_sliced.h, every row the same
-// element), as k_verify_comb_wide's decompression does.
-__global__ __launch_bounds__(64) void k_sign_wide(const SignKey* __restrict__ key, const ge_niels* __restrict__ table,
-                                                  const uint8_t* __restrict__ msgs, uint64_t stride, uint64_t n,
-                                                  uint8_t* __restrict__ sigs, uint8_t* __restrict__ flags) {
-  const uint64_t i = blockIdx.x;
-  if (i >= n) return;   // block-uniform
-  const int lane = threadIdx.x & 63;
+// Copies the table into the block's LDS (all of the block's threads call it).
+FE_DEV void sign_table_to_lds(const ge_niels* table, ge_niels* sT) {
+  for (int i = threadIdx.x; i < SIGN_TABLE_ENTRIES * 30; i += blockDim.x)
+    reinterpret_cast<i32*>(sT)[i] = reinterpret_cast<const i32*>(table)[i];
+  __syncthreads();
+}
+
+// Throughput kernel: lane i signs digest i (msgs + stride * i, stride 32 or 0).
+__global__ __launch_bounds__(256) void k_sign(const SignKey* __restrict__ key, const ge_niels* __restrict__ table,
+                                              const uint8_t* __restrict__ msgs, uint64_t stride, uint64_t n,
+                                              uint8_t* __restrict__ sigs, uint8_t* __restrict__ flags) {
+  __shared__ ge_niels sT[SIGN_TABLE_ENTRIES];
+  sign_table_to_lds(table, sT);
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
   u32 m[8];
   load_words8(msgs + stride * i, m);
+  sign_lane(key, sT, m, sigs, flags, i);
+}
+
+// One wave's signature of the digest m (every lane holds the same m).  Every lane derives r; lane
+// w takes window w's entry (all 8 candidates read, masked); the 64 points are summed by a 6-level
+// butterfly, after which every lane holds R; the inversion of Z runs limb-sliced (fe_sliced.h,
+// every row the same element), as k_verify_comb_wide's decompression does.  Lane 0 stores to
+// sigs + 64 i (and flags + i, when there are flags).  The body of k_sign_wide; the vote kernels
+// (vote.h) run it on Vote::digest.
+FE_DEV void sign_wave(const SignKey* key, const ge_niels* table, const u32 m[8], const int lane, uint8_t* sigs,
+                      uint8_t* flags, uint64_t i) {
   u32 r[8];
   sign_nonce(key, m, r);
   u32 dg[8];
@@ -262,6 +271,18 @@ __global__ __launch_bounds__(64) void k_sign_wide(const SignKey* __restrict__ ke
   u32 s[8];
   sign_response(key, R, m, r, s);
   if (lane == 0) sign_store(sigs + 64 * i, R, s, flags ? flags + i : nullptr);
+}
+
+// Latency kernel: block (one wave) i signs digest i.
+__global__ __launch_bounds__(64) void k_sign_wide(const SignKey* __restrict__ key, const ge_niels* __restrict__ table,
+                                                  const uint8_t* __restrict__ msgs, uint64_t stride, uint64_t n,
+                                                  uint8_t* __restrict__ sigs, uint8_t* __restrict__ flags) {
+  const uint64_t i = blockIdx.x;
+  if (i >= n) return;   // block-uniform
+  const int lane = threadIdx.x & 63;
+  u32 m[8];
+  load_words8(msgs + stride * i, m);
+  sign_wave(key, table, m, lane, sigs, flags, i);
 }
 
 }  // namespace nwc

@@ -25,6 +25,13 @@ constexpr uint64_t SIGN_HOST_CHUNK = 8192;
 static_assert((32 * SIGN_HOST_CHUNK) % 256 == 0 && 97 * SIGN_HOST_CHUNK <= NWC_PINNED_STAGE_MAX,
               "a chunk's digests, signatures and flags fit the pinned stage");
 
+// votes per pinned chunk of a host call (nwc_signer_vote_many): id, round and origin (72 B) in,
+// 64 B out and a flag byte each
+constexpr uint64_t VOTE_HOST_CHUNK = 4096;
+static_assert((32 * VOTE_HOST_CHUNK) % 256 == 0 && (8 * VOTE_HOST_CHUNK) % 256 == 0 &&
+                  (72 + 64 + 1) * VOTE_HOST_CHUNK <= NWC_PINNED_STAGE_MAX,
+              "a chunk's ids, rounds, origins, signatures and flags fit the pinned stage");
+
 void wipe(volatile uint8_t* p, size_t n) {
   for (size_t i = 0; i < n; ++i) p[i] = 0;
 }
@@ -88,6 +95,21 @@ int launch_sign(DevCtx& d, const nwc::SignKey* key, const uint8_t* msgs, uint64_
   else
     hipLaunchKernelGGL(nwc::k_sign, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, key, (const nwc::ge_niels*)d.sign_table,
                        msgs, stride, n, sigs, flags);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// Vote::new for n (id, round, origin) triples: k_vote_wide or k_vote (vote.h), chosen as launch_sign's caller does.
+int launch_vote(DevCtx& d, const nwc::SignKey* key, const uint8_t* ids, const uint64_t* rounds, const uint8_t* origins, uint64_t n,
+                uint8_t* sigs, uint8_t* flags, bool wide, hipStream_t s) {
+  if (n == 0) return 0;
+  if (n >= (1ull << 31)) return set_err(NWC_ERR_ARG, "n must be below 2^31 per call");
+  if (wide)
+    hipLaunchKernelGGL(nwc::k_vote_wide, dim3((unsigned)n), dim3(64), 0, s, key, (const nwc::ge_niels*)d.sign_table, ids, rounds,
+                       origins, n, sigs, flags);
+  else
+    hipLaunchKernelGGL(nwc::k_vote, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, key, (const nwc::ge_niels*)d.sign_table,
+                       ids, rounds, origins, n, sigs, flags);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -220,6 +242,60 @@ int nwc_dev_sign(void* signer, const void* d_msgs, uint64_t msg_stride, uint64_t
   HIP_TRY(hipSetDevice(d.hip_id));
   return launch_sign(d, sg.key, static_cast<const uint8_t*>(d_msgs), msg_stride, n, static_cast<uint8_t*>(d_sigs), nullptr,
                      sign_takes_wide(n), reinterpret_cast<hipStream_t>(stream));
+}
+
+int nwc_signer_vote_many(void* signer, const uint8_t* ids32, const uint64_t* rounds, const uint8_t* origins32, size_t n,
+                         uint8_t* sigs) {
+  if (n && (!ids32 || !rounds || !origins32 || !sigs)) return set_err(NWC_ERR_ARG, "null buffer");
+  SIGNER_PROLOGUE(signer);
+  if (n == 0) return 0;
+  DevCtx& d = *sg.d;
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.hip_id));
+  if (int rc = d.ensure_pinned(NWC_PINNED_STAGE_MAX)) return rc;
+  const bool spin = settings().spin_wait;
+  const bool wide = sign_takes_wide(n);
+  for (uint64_t lo = 0; lo < n; lo += VOTE_HOST_CHUNK) {
+    const uint64_t c = std::min<uint64_t>(VOTE_HOST_CHUNK, n - lo);
+    // ids | rounds | origins | signatures | flags, each from a 256-byte boundary
+    const size_t ro = align256(32 * c), oo = ro + align256(8 * c), so = oo + align256(32 * c), fo = so + align256(64 * c);
+    uint8_t* h = d.pinned;
+    uint8_t* g = d.pinned.dev();
+    std::memcpy(h, ids32 + 32 * lo, 32 * c);
+    std::memcpy(h + ro, rounds + lo, 8 * c);
+    std::memcpy(h + oo, origins32 + 32 * lo, 32 * c);
+    std::memset(h + fo, 0, c);
+    if (int rc = launch_vote(d, sg.key, g, reinterpret_cast<const uint64_t*>(g + ro), g + oo, c, g + so, g + fo, wide, d.stream))
+      return rc;
+    const bool poll = spin && c <= NWC_WIDE_MAX;
+    if (!poll || !nwc::plan::poll_written(h + fo, c, std::chrono::milliseconds(200))) {
+      HIP_TRY(hipStreamSynchronize(d.stream));
+      if (poll && !nwc::plan::poll_written(h + fo, c, std::chrono::microseconds(0)))
+        return set_err(NWC_ERR_DEVICE, "vote kernel left signatures unwritten");
+    }
+    std::memcpy(sigs + 64 * lo, h + so, 64 * c);
+  }
+  return 0;
+}
+
+int nwc_signer_vote(void* signer, const uint8_t id32[32], uint64_t round, const uint8_t origin32[32], uint8_t sig[64]) {
+  if (!id32 || !origin32 || !sig) return set_err(NWC_ERR_ARG, "null buffer");
+  return nwc_signer_vote_many(signer, id32, &round, origin32, 1, sig);
+}
+
+int nwc_dev_vote(void* signer, const void* d_ids, const void* d_rounds, const void* d_origins, uint64_t n, void* d_sigs,
+                 void* stream) {
+  if (n && (!d_ids || !d_rounds || !d_origins || !d_sigs)) return set_err(NWC_ERR_ARG, "null buffer");
+  SIGNER_PROLOGUE(signer);
+  if (((uintptr_t)d_ids & 15) || ((uintptr_t)d_origins & 15) || ((uintptr_t)d_rounds & 7) || ((uintptr_t)d_sigs & 3))
+    return set_err(NWC_ERR_ARG, "d_ids and d_origins must be 16-byte, d_rounds 8-byte and d_sigs 4-byte aligned");
+  if (n == 0) return 0;
+  DevCtx& d = *sg.d;
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.hip_id));
+  return launch_vote(d, sg.key, static_cast<const uint8_t*>(d_ids), static_cast<const uint64_t*>(d_rounds),
+                     static_cast<const uint8_t*>(d_origins), n, static_cast<uint8_t*>(d_sigs), nullptr, sign_takes_wide(n),
+                     reinterpret_cast<hipStream_t>(stream));
 }
 
 int nwc_signer_destroy(void* signer) {

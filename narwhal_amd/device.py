@@ -182,6 +182,23 @@ def sign(signer, msgs: torch.Tensor, out: Optional[torch.Tensor] = None, n: Opti
     return out
 
 
+def vote(signer, ids: torch.Tensor, rounds: torch.Tensor, origins: torch.Tensor,
+         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """nwc_dev_vote: Vote::new signatures [n, 64] for HBM-resident ids[n, 32] (uint8), rounds[n]
+    (int64, read as u64) and origins[n, 32] (uint8) under `signer`.  Asynchronous on the current stream."""
+    lib = _lib.load()
+    handle = getattr(signer, "handle", signer)
+    n = rounds.numel()
+    assert ids.dtype == torch.uint8 and origins.dtype == torch.uint8 and rounds.dtype == torch.int64
+    assert ids.numel() == 32 * n and origins.numel() == 32 * n
+    if out is None:
+        out = torch.empty((n, 64), dtype=torch.uint8, device=ids.device)
+    assert out.dtype == torch.uint8 and out.numel() >= 64 * n
+    _lib.check(lib.nwc_dev_vote(handle, _ptr(ids) if n else None, _ptr(rounds) if n else None, _ptr(origins) if n else None,
+                                n, _ptr(out) if n else None, _stream()))
+    return out
+
+
 def unpack_bits(words: torch.Tensor, n: int):
     """Verdict words -> numpy bool array of length n (host)."""
     import numpy as np

@@ -22,7 +22,7 @@ from dataclasses import dataclass, field
 from typing import Dict, Iterable, List, Optional, Sequence, Set, Tuple
 
 from . import _lib
-from .crypto import Digest, PublicKey, SecretKey, Signature, digest_bytes
+from .crypto import Digest, PublicKey, SecretKey, Signature, Signer, digest_bytes
 
 __all__ = ["DagError", "Authority", "Committee", "Header", "Vote", "Certificate", "sanitize_many",
            "Sanitizer", "DAG_ERRORS"]
@@ -137,9 +137,14 @@ class Vote:
     signature: Signature = field(default_factory=Signature)
 
     @classmethod
-    def new(cls, header: Header, author: PublicKey, secret: SecretKey) -> "Vote":
+    def new(cls, header: Header, author: PublicKey, secret) -> "Vote":
+        """Vote::new (messages.rs:115-129).  `secret`: a SecretKey, or a Signer (a registered key:
+        digest and signature in one launch, nwc_signer_vote)."""
         v = cls(header.id, header.round, header.author, author)
-        v.signature = Signature.new(v.digest(), secret)
+        if isinstance(secret, Signer):
+            v.signature = secret.vote(header.id, header.round, header.author)
+        else:
+            v.signature = Signature.new(v.digest(), secret)
         return v
 
     def digest(self) -> Digest:
@@ -216,6 +221,30 @@ class Sanitizer:
         code = self._lib.nwc_sanitizer_sanitize(self.handle, _lib.buf(wire) if wire else None, len(wire), gc_round,
                                                 _lib.buf(t) if t else None, dig, kind)
         return int(code), Digest(dig.raw), kind.raw[0]
+
+    def sanitize_vote(self, wire: bytes, signer: Signer, gc_round: int = 0,
+                      target: Optional[Header] = None) -> Tuple[int, Digest, int, Optional[Signature]]:
+        """`sanitize`, and for a header whose code is Ok the signature of Vote::new(header, ..) under
+        `signer`'s key from the same flight (nwc_sanitizer_sanitize_vote); None otherwise.  The
+        library keeps no voting state: Core's last_voted check stays with the caller."""
+        wire = bytes(wire)
+        t = None
+        if target is not None:
+            t = bytes(target.id) + struct.pack("<Q", target.round) + bytes(target.author)
+        dig = ctypes.create_string_buffer(32)
+        kind = ctypes.create_string_buffer(1)
+        sig = ctypes.create_string_buffer(64)
+        voted = ctypes.c_int32(0)
+        code = self._lib.nwc_sanitizer_sanitize_vote(self.handle, signer.handle, _lib.buf(wire) if wire else None,
+                                                     len(wire), gc_round, _lib.buf(t) if t else None, dig, kind, sig,
+                                                     ctypes.byref(voted))
+        return int(code), Digest(dig.raw), kind.raw[0], Signature.from_bytes(sig.raw) if voted.value else None
+
+    def vote_stats(self) -> dict:
+        """Votes signed inside a group flight / by the one-message fallback."""
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(self._lib.nwc_sanitizer_vote_stats(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return {"in_flight": int(a.value), "alone": int(b.value)}
 
     def check(self, wire: bytes, gc_round: int = 0, target: Optional[Header] = None) -> Tuple[Digest, int]:
         """`sanitize`, raising DagError for a code > 0 and DeviceError for a code < 0; (digest, kind)."""

@@ -54,6 +54,11 @@ extern "C" {
     pub fn nwc_signer_sign_many(signer: *mut c_void, msgs32: *const u8, n: usize, sigs: *mut u8) -> c_int;
     pub fn nwc_dev_sign(signer: *mut c_void, d_msgs: *const c_void, msg_stride: u64, n: u64, d_sigs: *mut c_void,
                         stream: *mut c_void) -> c_int;
+    pub fn nwc_signer_vote(signer: *mut c_void, id32: *const u8, round: u64, origin32: *const u8, sig: *mut u8) -> c_int;
+    pub fn nwc_signer_vote_many(signer: *mut c_void, ids32: *const u8, rounds: *const u64, origins32: *const u8, n: usize,
+                                sigs: *mut u8) -> c_int;
+    pub fn nwc_dev_vote(signer: *mut c_void, d_ids: *const c_void, d_rounds: *const c_void, d_origins: *const c_void, n: u64,
+                        d_sigs: *mut c_void, stream: *mut c_void) -> c_int;
     pub fn nwc_signer_destroy(signer: *mut c_void) -> c_int;
     pub fn nwc_verifier_create(max_requests: u32, max_wait_us: u32) -> *mut c_void;
     pub fn nwc_verifier_verify_strict(verifier: *mut c_void, msg32: *const u8, pk: *const u8, sig: *const u8) -> c_int;
@@ -65,6 +70,10 @@ extern "C" {
     pub fn nwc_sanitizer_sanitize(sanitizer: *mut c_void, msg: *const u8, len: usize, gc_round: u64, vote_target: *const u8,
                                   digest32: *mut u8, kind: *mut u8) -> c_int;
     pub fn nwc_sanitizer_stats(sanitizer: *mut c_void, out: *mut u64) -> c_int;
+    pub fn nwc_sanitizer_sanitize_vote(sanitizer: *mut c_void, signer: *mut c_void, msg: *const u8, len: usize, gc_round: u64,
+                                       vote_target: *const u8, digest32: *mut u8, kind: *mut u8, vote_sig64: *mut u8,
+                                       voted: *mut i32) -> c_int;
+    pub fn nwc_sanitizer_vote_stats(sanitizer: *mut c_void, in_flight: *mut u64, alone: *mut u64) -> c_int;
     pub fn nwc_sanitizer_destroy(sanitizer: *mut c_void) -> c_int;
     pub fn nwc_set_committee(pks: *const u8, n: usize) -> c_int;
     pub fn nwc_cache_stats(committee_keys: *mut u32, auto_keys: *mut u32) -> c_int;

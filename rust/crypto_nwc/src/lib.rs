@@ -234,6 +234,26 @@ impl Signer {
         });
         sigs
     }
+
+    /// `Vote::new(header, ..).signature` (primary/src/messages.rs:115-129) for a header the caller
+    /// has accepted: the signature of SHA-512(id || round LE || origin)[..32], digest and signature
+    /// in one launch.
+    pub fn vote(&self, id: &[u8; 32], round: u64, origin: &[u8; 32]) -> [u8; 64] {
+        let mut sig = [0u8; 64];
+        check(unsafe { ffi::nwc_signer_vote(self.h, id.as_ptr(), round, origin.as_ptr(), sig.as_mut_ptr()) });
+        sig
+    }
+
+    /// One launch for all of a round's votes: (ids[i], rounds[i], origins[i]) -> signature i.
+    pub fn vote_many(&self, ids: &[[u8; 32]], rounds: &[u64], origins: &[[u8; 32]]) -> Vec<[u8; 64]> {
+        assert!(ids.len() == rounds.len() && ids.len() == origins.len());
+        let mut sigs = vec![[0u8; 64]; ids.len()];
+        check(unsafe {
+            ffi::nwc_signer_vote_many(self.h, ids.as_ptr() as *const u8, rounds.as_ptr(), origins.as_ptr() as *const u8,
+                                      ids.len(), sigs.as_mut_ptr() as *mut u8)
+        });
+        sigs
+    }
 }
 
 impl Drop for Signer {
@@ -370,6 +390,32 @@ impl Sanitizer {
         check(rc);
         v.code = rc as u32;
         v
+    }
+
+    /// `sanitize`, and for a header whose code is Ok the signature of `Vote::new(header, ..)` under
+    /// `signer`'s key from the same flight.  The library keeps no voting state: Core's `last_voted`
+    /// check stays with the caller, and a vote is signed only after the header's code is Ok.
+    /// `signer` must live on the sanitizer's device.  Panics on a device failure.
+    pub fn sanitize_vote(&self, signer: &Signer, wire: &[u8], gc_round: u64,
+                         vote_target: Option<&[u8; 72]>) -> (Verdict, Option<[u8; 64]>) {
+        let mut v = Verdict { code: 0, digest: [0u8; 32], kind: 3 };
+        let mut sig = [0u8; 64];
+        let mut voted: i32 = 0;
+        let rc = unsafe {
+            ffi::nwc_sanitizer_sanitize_vote(self.h, signer.h, wire.as_ptr(), wire.len(), gc_round,
+                                             vote_target.map_or(std::ptr::null(), |t| t.as_ptr()), v.digest.as_mut_ptr(),
+                                             &mut v.kind, sig.as_mut_ptr(), &mut voted)
+        };
+        check(rc);
+        v.code = rc as u32;
+        (v, if voted != 0 { Some(sig) } else { None })
+    }
+
+    /// Votes signed inside a group flight / by the one-message fallback.
+    pub fn vote_stats(&self) -> (u64, u64) {
+        let (mut in_flight, mut alone) = (0u64, 0u64);
+        check(unsafe { ffi::nwc_sanitizer_vote_stats(self.h, &mut in_flight, &mut alone) });
+        (in_flight, alone)
     }
 
     pub fn stats(&self) -> SanitizerStats {
