@@ -469,6 +469,56 @@ int nwc_dev_sanitize_messages(const void* d_data, const void* d_offsets, uint64_
                               uint64_t gc_round, const uint8_t* vote_target, void* d_codes,
                               void* d_digests32, void* stream);
 
+/* The batch entry with Core's state per message and Vote::new from the same call: what a batching
+ * task needs when it drains frames across a state change.  Message i is judged
+ * under gc_rounds[i] and target record i; a NULL gc_rounds means gc_round for every message, a NULL
+ * vote_targets80 means vote_target (72 B or NULL, as nwc_sanitize_messages) for every message.  A
+ * target record is 80 bytes: id (32), round (u64 LE), origin (32), one "enabled" byte of which only
+ * bit 0 is read (0: no current header, every vote passes sanitize_vote's target check), seven zero
+ * bytes.  codes, digests32 (nullable) and kinds (nullable) of message i are exactly those of
+ * nwc_sanitize_messages on message i alone with that state; with both arrays NULL and no signer the
+ * outputs are byte-identical to nwc_sanitize_messages'.
+ *
+ * signer (a nwc_signer, or NULL): voted[i] = 1 and vote_sigs + 64 i holds
+ * Vote::new(header, signer's key).signature iff message i is a header and codes[i] is NWC_DAG_OK;
+ * otherwise voted[i] = 0 and the 64 bytes are zero.  On an error < 0 every vote output is zero.
+ * vote_sigs (m x 64 B) and voted (m bytes) are required with a signer (NWC_ERR_ARG) and untouched
+ * without one.  The two rules of nwc_sanitizer_sanitize_vote hold here as well:
+ *   - The library is stateless about voting: Core's last_voted check (core.rs:206-212) stays the
+ *     caller's duty, and a signature Core decides not to send is simply dropped.
+ *   - A vote is signed only AFTER the message's final code is Ok (one more launch behind the codes,
+ *     one wave per message), never speculatively on unverified wire bytes.
+ * A call without a signer builds no signing table and launches nothing more than
+ * nwc_sanitize_messages does.  The signer may not be destroyed while a call that carries it runs.
+ *
+ * Devices: a host call that carries a signer is not sharded; it runs whole on the signer's device.
+ * Calls without a signer shard as nwc_sanitize_messages does.  Conventions as everywhere here: null
+ * data, offsets or codes give NWC_ERR_ARG, NWC_ERR_NOT_INIT before nwc_init and before
+ * nwc_set_committee_config; m == 0 is a no-op returning 0 (whatever else is passed, a signer with
+ * NULL vote outputs excepted). */
+int nwc_sanitize_messages_ex(const uint8_t* data, const uint64_t* offsets, size_t m,
+                             const uint64_t* gc_rounds,      /* m values, or NULL: gc_round for every message */
+                             uint64_t gc_round,
+                             const uint8_t* vote_targets80,  /* m x 80 B, or NULL: vote_target for every message */
+                             const uint8_t* vote_target,     /* 72 B or NULL */
+                             void* signer,                   /* nwc_signer or NULL */
+                             int32_t* codes, uint8_t* digests32, uint8_t* kinds,
+                             uint8_t* vote_sigs,             /* m x 64 B, required with a signer */
+                             uint8_t* voted);                /* m bytes, required with a signer */
+
+/* Device-resident variant: d_data, d_offsets, total, d_codes, d_digests32 and stream as
+ * nwc_dev_sanitize_messages; d_gc_rounds (nullable, device u64[m], 8-byte aligned),
+ * d_vote_targets80 (nullable, device m x 80 B, 4-byte aligned), d_kinds (nullable, device m bytes),
+ * d_vote_sigs (device m x 64 B, 4-byte aligned) and d_voted (device m bytes) are the twins of the
+ * host entry's arrays; vote_target stays a host pointer.  With a signer, d_digests32 may be NULL
+ * and is otherwise 16-byte aligned.  The signer must live on the calling thread's device
+ * (nwc_dev_set_device; NWC_ERR_ARG otherwise).  Synchronises once (the vote count); the codes, the
+ * votes and the kinds are queued on `stream` behind it. */
+int nwc_dev_sanitize_messages_ex(const void* d_data, const void* d_offsets, uint64_t m, uint64_t total,
+                                 const void* d_gc_rounds, uint64_t gc_round, const void* d_vote_targets80,
+                                 const uint8_t* vote_target, void* signer, void* d_codes, void* d_digests32,
+                                 void* d_kinds, void* d_vote_sigs, void* d_voted, void* stream);
+
 /* ---- digests -------------------------------------------------------------------------- */
 /* Sha512::digest(bytes)[..32] -- worker/src/processor.rs:38 and crypto's `Hash for &[u8]`
  * (crypto/src/tests/crypto_tests.rs:8-12). */

@@ -105,6 +105,12 @@ _SIGS = {
                                                  ctypes.c_void_p]),
     "nwc_sanitize_messages": (ctypes.c_int, [_c_u8p, _c_u8p, ctypes.c_size_t, ctypes.c_uint64, _c_u8p, _c_u8p,
                                              _c_u8p, _c_u8p]),
+    "nwc_sanitize_messages_ex": (ctypes.c_int, [_c_u8p, _c_u8p, ctypes.c_size_t, _c_u8p, ctypes.c_uint64, _c_u8p, _c_u8p,
+                                                ctypes.c_void_p, _c_u8p, _c_u8p, _c_u8p, _c_u8p, _c_u8p]),
+    "nwc_dev_sanitize_messages_ex": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, _c_u8p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "nwc_digester_create": (ctypes.c_void_p, [ctypes.c_uint32, ctypes.c_uint32]),
     "nwc_digester_submit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64]),
     "nwc_digester_poll": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,

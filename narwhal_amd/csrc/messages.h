@@ -11,6 +11,8 @@
 //                        Certificate::digest (:226-234), evaluates the committee checks, and emits
 //                        the signature equations: one strict equation per message (the header's
 //                        or the vote's signature) and one batch-leaf equation per certificate vote.
+//   k_parse_messages_own the same with every message under its own gc_round and vote target
+//                        (nwc_sanitize_messages_ex); k_msg_kinds hands the kinds to a device caller.
 //   k_header_digests     one lane per message: Header::digest of the gathered input vs the id.
 //   k_finalize_messages  combines the flags with the equation verdicts into the DagError the
 //                        reference returns, in its order (primary/src/error.rs).
@@ -702,6 +704,37 @@ __global__ __launch_bounds__(64) void k_parse_messages(MsgArgs a, Committee cm, 
   const u32 lane = threadIdx.x;
   if (i >= a.m) return;   // block-uniform
   (void)parse_message(a, cm, cc, first, i, lane, UniformMsg{a, i});
+}
+
+// nwc_sanitize_messages_ex: k_parse_messages with every message under its own Core state.
+// gc_rounds[i] and the 80-byte record targets + 80 i (the group buffer's layout: id, round LE,
+// origin, then the "enabled" byte, of which bit 0 is read) belong to message i of THIS launch: a
+// chunk's launch passes both arrays moved up by its first message, as it does a.offsets.  Either
+// array may be null: the launch's a.gc_round / a.target then holds for every message.
+struct MsgOwnState {
+  const uint64_t* gc_rounds;
+  const uint8_t* targets;   // 4-byte aligned
+};
+__global__ __launch_bounds__(64) void k_parse_messages_own(MsgArgs a, Committee cm, CommitteeCfg cc, MsgOwnState o) {
+  extern __shared__ u32 first[];
+  const uint64_t i = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= a.m) return;   // block-uniform
+  VoteTarget t = a.target;
+  if (o.targets) {
+    const u32* tw = reinterpret_cast<const u32*>(o.targets + (size_t)80 * i);
+    _Pragma("unroll") for (int k = 0; k < 8; ++k) { t.id[k] = tw[k]; t.origin[k] = tw[10 + k]; }
+    t.round = (uint64_t)tw[8] | ((uint64_t)tw[9] << 32);
+    t.enabled = (int)(tw[18] & 1u);
+  }
+  const uint64_t gc = o.gc_rounds ? o.gc_rounds[i] : a.gc_round;
+  (void)parse_message(a, cm, cc, first, i, lane, OwnMsg{a.offsets[i], a.offsets[i + 1], gc, t});
+}
+
+// The kinds of a device-resident call, from the records (the host entries read the records back).
+__global__ __launch_bounds__(256) void k_msg_kinds(const uint32_t* __restrict__ rec, uint64_t m, uint8_t* __restrict__ kinds) {
+  const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < m) kinds[i] = (uint8_t)(rec[4 * i] & 255u);
 }
 
 // Header::digest of the gathered input, one lane per message (a header of 67 parents is 18 blocks)

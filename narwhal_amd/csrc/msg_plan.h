@@ -74,19 +74,33 @@ struct ArenaWalk {
 };
 
 // The call arena of a host call (byte offsets): the staged message bytes with 16 bytes of readable
-// padding, their offsets, and the codes, records and digests on their way back.
+// padding, their offsets, and the codes, records and digests on their way back.  What
+// nwc_sanitize_messages_ex adds lies behind them, so a call without it keeps the layout above:
+// with own_state the per-message gc_rounds (u64) and vote targets (80 B, SanGroupBuf's record), with
+// votes the Vote::new signatures (64 B) and the "voted" bytes on their way back.
 struct CallArena {
   size_t data, offsets, codes, rec, digests;
+  size_t gc_rounds, targets;      // own_state only
+  size_t vote_sigs, voted;        // votes only
   size_t bytes;
 };
-inline CallArena call_arena(size_t m, uint64_t total) {
+constexpr size_t MSG_TARGET_STRIDE = 80;
+inline CallArena call_arena(size_t m, uint64_t total, bool own_state = false, bool votes = false) {
   ArenaWalk w;
-  CallArena a;
+  CallArena a{};
   a.data = w.take(total + 16);
   a.offsets = w.take(8 * (m + 1));
   a.codes = w.take(4 * m);
   a.rec = w.take(16 * m);
   a.digests = w.take(32 * m);   // (reserved whether or not the caller asks for digests)
+  if (own_state) {
+    a.gc_rounds = w.take(8 * m);
+    a.targets = w.take(MSG_TARGET_STRIDE * m);
+  }
+  if (votes) {
+    a.vote_sigs = w.take(64 * m);
+    a.voted = w.take(m);
+  }
   a.bytes = w.off;
   return a;
 }
@@ -97,11 +111,13 @@ inline CallArena call_arena(size_t m, uint64_t total) {
 struct MsgArena {
   size_t hashbuf, eq_msg, eq_pk, eq_sig, cdig, v_pk, v_sig, v_msg, v_total, hmatch, rec, rec_n, sbits, lbits;
   size_t sr_x, sr_z, sr_p, sr_meta, srs_x, srs_z, srs_p, srs_meta;   // ysplit only
+  size_t digests;                                                    // own_digests only
   size_t bytes;
 };
 // own_rec: the records live here (a caller that supplies its own array leaves `rec` unused: the
-// fields after it move up, and its bytes are still counted).
-inline MsgArena msg_arena(size_t m, uint64_t total, uint64_t vt, bool ysplit, bool own_rec) {
+// fields after it move up, and its bytes are still counted).  own_digests: a call that signs votes
+// while its caller takes no digests keeps them here, behind everything else.
+inline MsgArena msg_arena(size_t m, uint64_t total, uint64_t vt, bool ysplit, bool own_rec, bool own_digests = false) {
   ArenaWalk w;
   MsgArena a{};
   a.hashbuf = w.take(total + 128 * (m + 2));
@@ -128,6 +144,7 @@ inline MsgArena msg_arena(size_t m, uint64_t total, uint64_t vt, bool ysplit, bo
     a.srs_p = w.take(32 * m);
     a.srs_meta = w.take(4 * m);
   }
+  if (own_digests) a.digests = w.take(32 * m);
   a.bytes = w.off + (own_rec ? 0 : align256(16 * m));
   return a;
 }

@@ -2452,8 +2452,8 @@ int nwc_set_committee_config(const uint8_t* pks, const uint64_t* stakes, size_t 
 }  // extern "C"
 
 #include "digester.h"
-#include "sanitizer.h"
 #include "signer.h"
+#include "sanitizer.h"
 #include "verifier.h"
 #include "sanitizer_handle.h"
 

@@ -1,7 +1,9 @@
-// Host side of the message pipeline (include/nwc.h nwc_sanitize_messages, nwc_dev_sanitize_messages;
-// kernels in messages.h).  Included by nwc_api.hip after the device contexts: uses
-// DevCtx, set_err, HIP_TRY, launch_verify and the deferred-list helpers.  Where a batch is cut, how
-// its arenas are laid out and what a call defers are msg_plan.h's decisions; this file enqueues.
+// Host side of the message pipeline (include/nwc.h nwc_sanitize_messages, nwc_dev_sanitize_messages
+// and their _ex twins with per-message Core state and Vote::new; kernels in messages.h and vote.h;
+// DESIGN §4.7, §4.13).  Included by nwc_api.hip after the device contexts and signer.h: uses
+// DevCtx, set_err, HIP_TRY, launch_verify, the deferred-list helpers, Signer and
+// ensure_sign_table.  Where a batch is cut, how its arenas are laid out and what a call defers are
+// msg_plan.h's decisions; this file enqueues.
 #pragma once
 
 namespace {
@@ -67,6 +69,19 @@ class ChunkFeed {
   std::thread copier_;   // last: it starts in the constructor and uses the members above
 };
 
+// What the _ex entries add to a call, as device pointers (all null: the plain call).  gc_rounds
+// and targets (80-byte records, MSG_TARGET_STRIDE) give message i its own Core state; key is the
+// signer's key record, and with it vote_sigs (m x 64 B) and voted (m bytes) are written by
+// k_vote_msgs behind the codes; kinds (m bytes) is the device entry's twin of the host's kinds.
+struct MsgEx {
+  const uint64_t* gc_rounds = nullptr;
+  const uint8_t* targets = nullptr;
+  const nwc::SignKey* key = nullptr;
+  uint8_t* vote_sigs = nullptr;
+  uint8_t* voted = nullptr;
+  uint8_t* kinds = nullptr;
+};
+
 // Device part of nwc_sanitize_messages: messages in HBM (ddata 4-byte aligned with >= 16 bytes
 // of readable padding, doff device u64[m+1] relative to ddata, `total` bytes), parsed as the
 // chunks cuts[k] .. cuts[k+1] (whole messages).  `feed`, when given, is the host path's copies:
@@ -92,6 +107,7 @@ struct MsgPipeline {
   // leaves waited behind the markers of the in-flight copies, profiles/r05/wire_host.md)
   hipStream_t ls = nullptr;
   nwc::MsgArgs a{};                  // the whole call's arrays
+  MsgEx ex{};                        // per-message state and votes (nwc_sanitize_messages_ex)
   uint64_t vt = 0;                   // vote slots
   nwc::SignRecs sr{};                // vote v's record at index v
   nwc::SignRecs srs{};               // the strict equations' records (message i at index i)
@@ -133,17 +149,20 @@ struct MsgPipeline {
 
   // The schedule, the message arena, its memsets and the deferred list's reset.
   int setup(const uint8_t* ddata, const uint64_t* doff_, size_t m, uint64_t total, uint64_t gc_round,
-            const uint8_t* vote_target, int32_t* dcodes_, uint8_t* ddigests_, uint32_t* drec) {
+            const uint8_t* vote_target, int32_t* dcodes_, uint8_t* ddigests_, uint32_t* drec, const MsgEx& ex_ = {}) {
     if (int rc = ensure_verify_tables(d)) return rc;
+    ex = ex_;
     vt = nwc::plan::vote_slots(total, nch);
     if (!vt) return set_err(NWC_ERR_ARG, "too many vote slots in one call");
     sch = nwc::plan::schedule(nch, deferrable_list(d), g_cm_is_config.load(), settings());
-    const nwc::plan::MsgArena L = nwc::plan::msg_arena(m, total, vt, sch.ysplit, !drec);
+    // a call that signs votes publishes the digests (the votes' ids) whether or not its caller takes them
+    const bool own_digests = ex.key && !ddigests_;
+    const nwc::plan::MsgArena L = nwc::plan::msg_arena(m, total, vt, sch.ysplit, !drec, own_digests);
     if (int rc = ensure_idle(d, d.msg_arena, L.bytes, &s, L.bytes / 4 + (1 << 20))) return rc;
     uint8_t* const base = d.msg_arena;
     doff = doff_;
     dcodes = dcodes_;
-    ddigests = ddigests_;
+    ddigests = own_digests ? arena_at<uint8_t>(base, L.digests) : ddigests_;
     a.data = ddata;
     a.offsets = doff;
     a.m = m;
@@ -277,7 +296,14 @@ struct MsgPipeline {
     ak.rec = a.rec + 4 * c0;
     ak.rec_n = a.rec_n + c0;
     ak.digests = ddigests ? ddigests + 32 * c0 : nullptr;
-    hipLaunchKernelGGL(nwc::k_parse_messages, dim3((unsigned)ak.m), dim3(64), first_lds, s, ak, cm, cc);
+    if (ex.gc_rounds || ex.targets) {
+      // the chunk's own state from its first message, as its offsets
+      const nwc::MsgOwnState own{ex.gc_rounds ? ex.gc_rounds + c0 : nullptr,
+                                 ex.targets ? ex.targets + nwc::plan::MSG_TARGET_STRIDE * c0 : nullptr};
+      hipLaunchKernelGGL(nwc::k_parse_messages_own, dim3((unsigned)ak.m), dim3(64), first_lds, s, ak, cm, cc, own);
+    } else {
+      hipLaunchKernelGGL(nwc::k_parse_messages, dim3((unsigned)ak.m), dim3(64), first_lds, s, ak, cm, cc);
+    }
     HIP_TRY(hipGetLastError());
     if (nch > 1) {
       // the next chunk's votes from a 64-slot boundary: every leaf launch starts on its own
@@ -368,6 +394,16 @@ struct MsgPipeline {
     hipLaunchKernelGGL(nwc::k_finalize_messages, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, s, a.rec,
                        a.rec_n, a.hmatch, sbits, lbits, (uint64_t)a.m, dcodes);
     HIP_TRY(hipGetLastError());
+    if (ex.key) {
+      // Vote::new for the headers whose final code is Ok, once, over the whole call
+      hipLaunchKernelGGL(nwc::k_vote_msgs, dim3((unsigned)a.m), dim3(64), 0, s, ex.key, (const nwc::ge_niels*)d.sign_table, dcodes,
+                         a.rec, ddigests, a.eq_pk, a.data, doff, (uint64_t)a.m, ex.vote_sigs, ex.voted);
+      HIP_TRY(hipGetLastError());
+    }
+    if (ex.kinds) {
+      hipLaunchKernelGGL(nwc::k_msg_kinds, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, s, a.rec, (uint64_t)a.m, ex.kinds);
+      HIP_TRY(hipGetLastError());
+    }
     mark("final queued");
     if (timing && nch > 1) {
       std::string line;
@@ -380,16 +416,26 @@ struct MsgPipeline {
 
 int sanitize_dev(DevCtx& d, const uint8_t* ddata, const uint64_t* doff, size_t m, uint64_t total,
                  const std::vector<size_t>& cuts, uint64_t gc_round, const uint8_t* vote_target, int32_t* dcodes,
-                 uint8_t* ddigests, uint32_t* drec, hipStream_t s, ChunkFeed* feed = nullptr) {
+                 uint8_t* ddigests, uint32_t* drec, hipStream_t s, ChunkFeed* feed = nullptr, const MsgEx& ex = {}) {
   MsgPipeline p(d, s, cuts, feed);
-  if (int rc = p.setup(ddata, doff, m, total, gc_round, vote_target, dcodes, ddigests, drec)) return rc;
+  if (int rc = p.setup(ddata, doff, m, total, gc_round, vote_target, dcodes, ddigests, drec, ex)) return rc;
   return p.run();
 }
+
+// What an _ex call adds to a host call, as host pointers (key: the device's key record): the
+// per-message state goes up with the offsets, the votes come back with the codes.
+struct HostEx {
+  const uint64_t* gc_rounds = nullptr;
+  const uint8_t* targets = nullptr;
+  const nwc::SignKey* key = nullptr;
+  uint8_t* vote_sigs = nullptr;
+  uint8_t* voted = nullptr;
+};
 
 // One device's share of a host call: stages the messages (small batches in one copy, large ones
 // chunk by chunk through a ChunkFeed), runs the pipeline and reads the codes, kinds and digests back.
 int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t m, uint64_t gc_round,
-                   const uint8_t* vote_target, int32_t* codes, uint8_t* digests32, uint8_t* kinds) {
+                   const uint8_t* vote_target, int32_t* codes, uint8_t* digests32, uint8_t* kinds, const HostEx& hx = {}) {
   if (m == 0) return 0;
   const uint64_t base = offsets[0], total = offsets[m] - base;
   DevCtx& d = *ctx(di);
@@ -398,14 +444,23 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
   if (int rc = ensure_verify_tables(d)) return rc;
   if (!d.cc_stakes) return set_err(NWC_ERR_NOT_INIT, "nwc_set_committee_config has not been called");
   // staging area (the arena): message bytes, offsets, codes, records, digests
-  const nwc::plan::CallArena L = nwc::plan::call_arena(m, total);
+  const bool own_state = hx.gc_rounds || hx.targets;
+  const nwc::plan::CallArena L = nwc::plan::call_arena(m, total, own_state, hx.key != nullptr);
   if (int rc = d.ensure_arena(L.bytes)) return rc;
+  if (hx.key)
+    if (int rc = ensure_sign_table(d)) return rc;
   uint8_t* const arena = d.arena;
   uint8_t* ddata = arena_at<uint8_t>(arena, L.data);
   uint64_t* doff = arena_at<uint64_t>(arena, L.offsets);
   int32_t* dcodes = arena_at<int32_t>(arena, L.codes);
   uint32_t* drec = arena_at<uint32_t>(arena, L.rec);
-  uint8_t* ddig = digests32 ? arena_at<uint8_t>(arena, L.digests) : nullptr;
+  uint8_t* ddig = (digests32 || hx.key) ? arena_at<uint8_t>(arena, L.digests) : nullptr;
+  MsgEx ex;
+  ex.key = hx.key;
+  if (hx.key) {
+    ex.vote_sigs = arena_at<uint8_t>(arena, L.vote_sigs);
+    ex.voted = arena_at<uint8_t>(arena, L.voted);
+  }
   std::vector<uint64_t> hoff(m + 1);
   for (size_t i = 0; i <= m; ++i) hoff[i] = offsets[i] - base;
   // The chunks share the message offsets (uploaded first, relative to ddata) and the message arena
@@ -424,9 +479,20 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
   } else {
     HIP_TRY(hipMemcpyAsync(doff, hoff.data(), 8 * (m + 1), hipMemcpyHostToDevice, d.stream));
   }
+  // the per-message state with the offsets: on the call's stream, before the first parse
+  if (hx.gc_rounds) {
+    uint64_t* dgc = arena_at<uint64_t>(arena, L.gc_rounds);
+    HIP_TRY(hipMemcpyAsync(dgc, hx.gc_rounds, 8 * m, hipMemcpyHostToDevice, d.stream));
+    ex.gc_rounds = dgc;
+  }
+  if (hx.targets) {
+    uint8_t* dtg = arena_at<uint8_t>(arena, L.targets);
+    HIP_TRY(hipMemcpyAsync(dtg, hx.targets, nwc::plan::MSG_TARGET_STRIDE * m, hipMemcpyHostToDevice, d.stream));
+    ex.targets = dtg;
+  }
   if (!staged) {
     HIP_TRY(hipMemcpyAsync(ddata, data + base, total, hipMemcpyHostToDevice, d.stream));
-    if (int rc = sanitize_dev(d, ddata, doff, m, total, {0, m}, gc_round, vote_target, dcodes, ddig, drec, d.stream))
+    if (int rc = sanitize_dev(d, ddata, doff, m, total, {0, m}, gc_round, vote_target, dcodes, ddig, drec, d.stream, nullptr, ex))
       return rc;
   } else {
     if (int rc = ensure_stager(d)) return rc;
@@ -437,7 +503,7 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
     d.stager->reset();
     const auto tm0 = std::chrono::steady_clock::now();
     ChunkFeed feed(d, ddata, data + base, hoff, cuts);
-    int rc = sanitize_dev(d, ddata, doff, m, total, cuts, gc_round, vote_target, dcodes, ddig, drec, d.stream, &feed);
+    int rc = sanitize_dev(d, ddata, doff, m, total, cuts, gc_round, vote_target, dcodes, ddig, drec, d.stream, &feed, ex);
     feed.join();
     if (rc) {
       (void)hipStreamSynchronize(d.xfer);   // no copy still writes the arena when the call returns
@@ -459,6 +525,10 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
     HIP_TRY(hipMemcpyAsync(rec.data(), drec, 16 * m, hipMemcpyDeviceToHost, d.stream));
   }
   if (digests32) HIP_TRY(hipMemcpyAsync(digests32, ddig, 32 * m, hipMemcpyDeviceToHost, d.stream));
+  if (hx.key) {
+    HIP_TRY(hipMemcpyAsync(hx.vote_sigs, ex.vote_sigs, 64 * m, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipMemcpyAsync(hx.voted, ex.voted, m, hipMemcpyDeviceToHost, d.stream));
+  }
   HIP_TRY(hipStreamSynchronize(d.stream));
   if (kinds)
     for (size_t i = 0; i < m; ++i) kinds[i] = (uint8_t)rec[4 * i];
@@ -497,6 +567,93 @@ int nwc_dev_sanitize_messages(const void* d_data, const void* d_offsets, uint64_
   return sanitize_dev(d, static_cast<const uint8_t*>(d_data), static_cast<const uint64_t*>(d_offsets), m, total,
                       {0, (size_t)m}, gc_round, vote_target, static_cast<int32_t*>(d_codes), static_cast<uint8_t*>(d_digests32),
                       nullptr, stream ? static_cast<hipStream_t>(stream) : d.stream);
+}
+
+int nwc_sanitize_messages_ex(const uint8_t* data, const uint64_t* offsets, size_t m, const uint64_t* gc_rounds,
+                             uint64_t gc_round, const uint8_t* vote_targets80, const uint8_t* vote_target, void* signer,
+                             int32_t* codes, uint8_t* digests32, uint8_t* kinds, uint8_t* vote_sigs, uint8_t* voted) {
+  // on an error < 0 every vote output is zero
+  auto fail = [&](int rc) {
+    if (signer && m && vote_sigs) std::memset(vote_sigs, 0, 64 * m);
+    if (signer && m && voted) std::memset(voted, 0, m);
+    return rc;
+  };
+  if (signer && (!vote_sigs || !voted)) return fail(set_err(NWC_ERR_ARG, "a signer needs vote_sigs and voted"));
+  if (m == 0) return 0;
+  if (int rc = require_init()) return fail(rc);
+  if (!data || !offsets || !codes) return fail(set_err(NWC_ERR_ARG, "null buffer"));
+  for (size_t i = 0; i < m; ++i)
+    if (offsets[i + 1] < offsets[i]) return fail(set_err(NWC_ERR_ARG, "offsets not monotone at %zu", i));
+  HostEx hx;
+  hx.gc_rounds = gc_rounds;
+  hx.targets = vote_targets80;
+  if (!signer) {
+    // messages are independent: contiguous ranges per device, as nwc_sanitize_messages
+    return shard(m, [&](int di, uint64_t lo, uint64_t hi) -> int {
+      HostEx h = hx;
+      if (h.gc_rounds) h.gc_rounds += lo;
+      if (h.targets) h.targets += nwc::plan::MSG_TARGET_STRIDE * lo;
+      return sanitize_range(di, data, offsets + lo, hi - lo, gc_round, vote_target, codes + lo,
+                            digests32 ? digests32 + 32 * lo : nullptr, kinds ? kinds + lo : nullptr, h);
+    });
+  }
+  // with a signer: whole, on the signer's device (its key record lives there)
+  Signer& sg = *static_cast<Signer*>(signer);
+  if (!sg.d || !sg.key) return fail(set_err(NWC_ERR_NOT_INIT, "the signer's device context was shut down"));
+  int di = -1;
+  for (size_t k = 0; k < g_devs.size(); ++k)
+    if (g_devs[k].get() == sg.d) di = (int)k;
+  if (di < 0) return fail(set_err(NWC_ERR_ARG, "the signer's device is not initialised"));
+  hx.key = sg.key;
+  hx.vote_sigs = vote_sigs;
+  hx.voted = voted;
+  const int rc = sanitize_range(di, data, offsets, m, gc_round, vote_target, codes, digests32, kinds, hx);
+  return rc < 0 ? fail(rc) : rc;
+}
+
+int nwc_dev_sanitize_messages_ex(const void* d_data, const void* d_offsets, uint64_t m, uint64_t total,
+                                 const void* d_gc_rounds, uint64_t gc_round, const void* d_vote_targets80,
+                                 const uint8_t* vote_target, void* signer, void* d_codes, void* d_digests32, void* d_kinds,
+                                 void* d_vote_sigs, void* d_voted, void* stream) {
+  if (signer && (!d_vote_sigs || !d_voted)) return set_err(NWC_ERR_ARG, "a signer needs d_vote_sigs and d_voted");
+  if (m == 0) return 0;
+  if (int rc = require_init()) return rc;
+  DevCtx& d = *ctx(t_dev < (int)g_devs.size() ? t_dev : 0);
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.hip_id));
+  const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : d.stream;
+  // on an error < 0 every vote output is zero (queued on the call's stream)
+  auto fail = [&](int rc) {
+    if (signer) {
+      (void)hipMemsetAsync(d_vote_sigs, 0, 64 * m, s);
+      (void)hipMemsetAsync(d_voted, 0, m, s);
+    }
+    return rc;
+  };
+  if (!d_data || !d_offsets || !d_codes) return fail(set_err(NWC_ERR_ARG, "null buffer"));
+  if ((reinterpret_cast<uintptr_t>(d_data) & 3) != 0) return fail(set_err(NWC_ERR_ARG, "d_data must be 4-byte aligned"));
+  if ((reinterpret_cast<uintptr_t>(d_gc_rounds) & 7) || (reinterpret_cast<uintptr_t>(d_vote_targets80) & 3))
+    return fail(set_err(NWC_ERR_ARG, "d_gc_rounds must be 8-byte and d_vote_targets80 4-byte aligned"));
+  if (signer && ((reinterpret_cast<uintptr_t>(d_vote_sigs) & 3) || (reinterpret_cast<uintptr_t>(d_digests32) & 15)))
+    return fail(set_err(NWC_ERR_ARG, "with a signer d_vote_sigs must be 4-byte and d_digests32 16-byte aligned"));
+  if (!d.cc_stakes) return fail(set_err(NWC_ERR_NOT_INIT, "nwc_set_committee_config has not been called"));
+  MsgEx ex;
+  ex.gc_rounds = static_cast<const uint64_t*>(d_gc_rounds);
+  ex.targets = static_cast<const uint8_t*>(d_vote_targets80);
+  ex.kinds = static_cast<uint8_t*>(d_kinds);
+  if (signer) {
+    Signer& sg = *static_cast<Signer*>(signer);
+    if (!sg.d || !sg.key) return fail(set_err(NWC_ERR_NOT_INIT, "the signer's device context was shut down"));
+    if (sg.d != &d) return fail(set_err(NWC_ERR_ARG, "the signer lives on another device than the calling thread's"));
+    if (int rc = ensure_sign_table(d)) return fail(rc);
+    ex.key = sg.key;
+    ex.vote_sigs = static_cast<uint8_t*>(d_vote_sigs);
+    ex.voted = static_cast<uint8_t*>(d_voted);
+  }
+  const int rc = sanitize_dev(d, static_cast<const uint8_t*>(d_data), static_cast<const uint64_t*>(d_offsets), m, total,
+                              {0, (size_t)m}, gc_round, vote_target, static_cast<int32_t*>(d_codes),
+                              static_cast<uint8_t*>(d_digests32), nullptr, s, nullptr, ex);
+  return rc < 0 ? fail(rc) : rc;
 }
 
 }  // extern "C"

@@ -5,6 +5,8 @@
 //   k_vote_wide   latency: one wave per vote (as k_sign_wide)
 //   k_vote_group  the sanitizer's group flight: one wave per message of the group, after
 //                 k_finalize_group; signs for the headers whose code is Ok and whose caller asked
+//   k_vote_msgs   the batch entries (nwc_sanitize_messages_ex with a signer): one wave per message
+//                 of the call, after k_finalize_messages; signs for the headers whose code is Ok
 //   k_vote_wire   one wire header the host has already accepted (the queue's fallback)
 //
 // Every kernel is vote_digest (digest72 of messages.h, one SHA-512 block) followed by the signing
@@ -88,6 +90,44 @@ __global__ __launch_bounds__(64) void k_vote_group(const ge_niels* __restrict__ 
   load_words8(eq_pk + 32 * (size_t)i, origin);
   vote_digest(id, round, origin, m);
   sign_wave(reinterpret_cast<const SignKey*>(kaddr), table, m, (int)(threadIdx.x & 63), v.sigs, v.flags, i);
+}
+
+// The batch entries' votes (nwc_sanitize_messages_ex with a signer): after k_finalize_messages on
+// the call's stream, block (one wave) i for message i of the call.  Every block writes its slot:
+// voted[i] = 1 and the signature for a header whose final code is Ok, zeros otherwise -- the
+// outputs need no memset, and nothing is signed before codes[i] says Ok.  The header's id is the
+// digest the pipeline published (equal to the id on the wire, since the code is Ok), its origin
+// the parsed author at eq_pk + 32 i and its round the u64 behind the author string, read only
+// when it lies inside the message.  Every exit is block-uniform: codes, rec and the wire lengths
+// are the same in every lane.  sigs is 4-byte aligned.
+__global__ __launch_bounds__(64) void k_vote_msgs(const SignKey* __restrict__ key, const ge_niels* __restrict__ table,
+                                                  const int32_t* __restrict__ codes, const uint32_t* __restrict__ rec,
+                                                  const uint8_t* __restrict__ digests, const uint8_t* __restrict__ eq_pk,
+                                                  const uint8_t* __restrict__ data, const uint64_t* __restrict__ offsets,
+                                                  uint64_t m, uint8_t* __restrict__ sigs, uint8_t* __restrict__ voted) {
+  const uint64_t i = blockIdx.x;
+  if (i >= m) return;   // block-uniform, as every exit below
+  const int lane = (int)(threadIdx.x & 63);
+  bool vote = codes[i] == (int32_t)DAG_OK && (rec[4 * i] & 255u) == MSG_HEADER;
+  uint64_t beg = 0, L = 0;
+  if (vote) {
+    beg = offsets[i];
+    const uint64_t len = offsets[i + 1] - beg;
+    L = len >= 12 ? ld_u64(data, beg + 4) : ~0ull;
+    vote = L <= len && 20 + L <= len;   // (a header that parsed holds its round; never read past the message)
+  }
+  if (!vote) {
+    if (lane < 16) reinterpret_cast<uint32_t*>(sigs + 64 * i)[lane] = 0u;
+    if (lane == 0) voted[i] = 0;
+    return;
+  }
+  const uint64_t round = ld_u64(data, beg + 12 + L);
+  u32 id[8], origin[8], dg[8];
+  load_words8(digests + 32 * i, id);
+  load_words8(eq_pk + 32 * i, origin);
+  vote_digest(id, round, origin, dg);
+  sign_wave(key, table, dg, lane, sigs, nullptr, i);
+  if (lane == 0) voted[i] = 1;
 }
 
 // One wire message the host has sanitized to Ok + header (its id is `id32`): msg is 16-byte

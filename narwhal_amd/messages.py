@@ -10,6 +10,8 @@ Certificate digests, committee checks and all signatures on the device).
   Committee    config/src/lib.rs:134-212  authorities {PublicKey: Authority(stake, workers)}
   DagError     primary/src/error.rs  verification failures (code + variant name)
   sanitize_many(messages, committee, gc_round, current_header) -> [DagError | None]
+  sanitize_many_ex(messages, committee, states, gc_round, target, signer)
+                                     -> [(DagError | None, Digest, kind, Signature | None)]
 Wire format = bincode of `PrimaryMessage` (primary/src/primary.rs:33-38), built by `to_bytes()`.
 The object-level `verify` / `digest` calls go through the same GPU batch path (a batch of one);
 there is no CPU verification path.
@@ -25,7 +27,7 @@ from . import _lib
 from .crypto import Digest, PublicKey, SecretKey, Signature, Signer, digest_bytes
 
 __all__ = ["DagError", "Authority", "Committee", "Header", "Vote", "Certificate", "sanitize_many",
-           "Sanitizer", "DAG_ERRORS"]
+           "sanitize_many_ex", "Sanitizer", "DAG_ERRORS"]
 
 DAG_ERRORS = ["Ok", "InvalidSignature", "InvalidHeaderId", "MalformedHeader", "UnknownAuthority",
               "AuthorityReuse", "CertificateRequiresQuorum", "TooOld", "SerializationError", "UnexpectedVote",
@@ -309,3 +311,50 @@ def sanitize_many(messages: Sequence[bytes], committee: Committee, gc_round: int
         raw = dig.raw   # one copy (`.raw` copies the whole buffer on every access)
         digests.extend(Digest(raw[32 * i:32 * i + 32]) for i in range(m))
     return [None if c == 0 else DagError(c) for c in codes]
+
+
+def _target72(h: Optional[Header]) -> Optional[bytes]:
+    return None if h is None else bytes(h.id) + struct.pack("<Q", h.round) + bytes(h.author)
+
+
+def sanitize_many_ex(messages: Sequence[bytes], committee: Committee,
+                     states: Optional[Sequence[Tuple[int, Optional[Header]]]] = None, gc_round: int = 0,
+                     target: Optional[Header] = None,
+                     signer: Optional[Signer] = None) -> List[Tuple[Optional[DagError], Digest, int, Optional[Signature]]]:
+    """`sanitize_many` with Core's state per message and Vote::new from the same call
+    (nwc_sanitize_messages_ex).  `states`: per message the (gc_round, current header or None) that
+    held when the frame was received; None judges every message under `gc_round` and `target`.
+    `signer`: a registered key; every header whose verdict is Ok then comes back with the signature
+    of Vote::new(header, signer's key).  Returns per message (DagError or None, digest, kind,
+    Signature or None).  The library keeps no voting state: Core's last_voted check stays with the
+    caller."""
+    lib = _lib.load()
+    committee.install()
+    m = len(messages)
+    if m == 0:
+        return []
+    if states is not None and len(states) != m:
+        raise ValueError("states: one (gc_round, current header) per message")
+    offs = [0]
+    for b in messages:
+        offs.append(offs[-1] + len(b))
+    data = b"".join(messages) or b"\0"
+    offsets = (ctypes.c_uint64 * (m + 1))(*offs)
+    codes = (ctypes.c_int32 * m)()
+    dig = ctypes.create_string_buffer(32 * m)
+    kinds = ctypes.create_string_buffer(m)
+    gcs = recs = None
+    if states is not None:
+        gcs = (ctypes.c_uint64 * m)(*[int(s[0]) for s in states])
+        # the 80-byte record: id, round LE, origin, the "enabled" byte, seven zero bytes
+        recs = b"".join(bytes(80) if s[1] is None else _target72(s[1]) + b"\x01" + bytes(7) for s in states)
+    sigs = ctypes.create_string_buffer(64 * m) if signer is not None else None
+    voted = ctypes.create_string_buffer(m) if signer is not None else None
+    t = _target72(target)
+    _lib.check(lib.nwc_sanitize_messages_ex(_lib.buf(data), offsets, m, gcs, gc_round, _lib.buf(recs) if recs else None,
+                                            _lib.buf(t) if t else None, signer.handle if signer is not None else None,
+                                            codes, dig, kinds, sigs, voted))
+    raw, kraw = dig.raw, kinds.raw
+    sraw, vraw = (sigs.raw, voted.raw) if signer is not None else (b"", bytes(m))
+    return [(None if codes[i] == 0 else DagError(codes[i]), Digest(raw[32 * i:32 * i + 32]), kraw[i],
+             Signature.from_bytes(sraw[64 * i:64 * i + 64]) if vraw[i] else None) for i in range(m)]

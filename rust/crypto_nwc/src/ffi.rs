@@ -90,6 +90,15 @@ extern "C" {
     pub fn nwc_dev_sanitize_messages(d_data: *const c_void, d_offsets: *const c_void, m: u64, total: u64, gc_round: u64,
                                      vote_target: *const u8, d_codes: *mut c_void, d_digests32: *mut c_void,
                                      stream: *mut c_void) -> c_int;
+    pub fn nwc_sanitize_messages_ex(data: *const u8, offsets: *const u64, m: usize, gc_rounds: *const u64, gc_round: u64,
+                                    vote_targets80: *const u8, vote_target: *const u8, signer: *mut c_void,
+                                    codes: *mut i32, digests32: *mut u8, kinds: *mut u8, vote_sigs: *mut u8,
+                                    voted: *mut u8) -> c_int;
+    pub fn nwc_dev_sanitize_messages_ex(d_data: *const c_void, d_offsets: *const c_void, m: u64, total: u64,
+                                        d_gc_rounds: *const c_void, gc_round: u64, d_vote_targets80: *const c_void,
+                                        vote_target: *const u8, signer: *mut c_void, d_codes: *mut c_void,
+                                        d_digests32: *mut c_void, d_kinds: *mut c_void, d_vote_sigs: *mut c_void,
+                                        d_voted: *mut c_void, stream: *mut c_void) -> c_int;
 
     pub fn nwc_digest32(data: *const u8, len: usize, out32: *mut u8) -> c_int;
     pub fn nwc_sha512_trunc32_many(data: *const u8, offsets: *const u64, n: usize, out32: *mut u8) -> c_int;

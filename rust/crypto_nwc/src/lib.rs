@@ -430,3 +430,70 @@ impl Drop for Sanitizer {
         unsafe { ffi::nwc_sanitizer_destroy(self.h) };
     }
 }
+
+/// Core's state as it was when one frame was received: `gc_round`, and for votes the current
+/// header (`id || round (LE) || author`, 72 bytes; `None`: no current header).
+#[derive(Debug, Clone, Copy)]
+pub struct FrameState<'a> {
+    pub gc_round: u64,
+    pub vote_target: Option<&'a [u8; 72]>,
+}
+
+/// The batch entry with Core's state per message and `Vote::new` from the same call
+/// (`nwc_sanitize_messages_ex`): what a batching task calls with the frames it drained, each with
+/// the `FrameState` recorded when it arrived.  Message `i` is `wires[i]`; its
+/// verdict is that of `nwc_sanitize_messages` on it alone under `states[i]`.  With a `signer`,
+/// every header whose code is Ok comes back with the signature of `Vote::new(header, ..)` under
+/// the signer's key; the call then runs whole on the signer's device.  The library keeps no voting
+/// state: Core's `last_voted` check stays with the caller, and a vote is signed only after the
+/// header's code is Ok.  The committee is the one last given to `nwc_set_committee_config`.
+/// Panics on a device failure.
+pub fn sanitize_batch(wires: &[&[u8]], states: &[FrameState], signer: Option<&Signer>) -> Vec<(Verdict, Option<[u8; 64]>)> {
+    assert_eq!(wires.len(), states.len());
+    init(0);
+    let m = wires.len();
+    if m == 0 {
+        return Vec::new();
+    }
+    let mut offsets = Vec::with_capacity(m + 1);
+    let mut data = Vec::new();
+    offsets.push(0u64);
+    for w in wires {
+        data.extend_from_slice(w);
+        offsets.push(data.len() as u64);
+    }
+    data.push(0);   // never an empty buffer
+    let gc_rounds: Vec<u64> = states.iter().map(|s| s.gc_round).collect();
+    // the 80-byte record: id, round LE, origin, the "enabled" byte, seven zero bytes
+    let mut targets = vec![0u8; 80 * m];
+    for (i, s) in states.iter().enumerate() {
+        if let Some(t) = s.vote_target {
+            targets[80 * i..80 * i + 72].copy_from_slice(t);
+            targets[80 * i + 72] = 1;
+        }
+    }
+    let mut codes = vec![0i32; m];
+    let mut digests = vec![0u8; 32 * m];
+    let mut kinds = vec![3u8; m];
+    let mut sigs = vec![0u8; 64 * m];
+    let mut voted = vec![0u8; m];
+    let rc = unsafe {
+        ffi::nwc_sanitize_messages_ex(data.as_ptr(), offsets.as_ptr(), m, gc_rounds.as_ptr(), 0, targets.as_ptr(), std::ptr::null(),
+                                      signer.map_or(std::ptr::null_mut(), |s| s.h), codes.as_mut_ptr(), digests.as_mut_ptr(),
+                                      kinds.as_mut_ptr(), if signer.is_some() { sigs.as_mut_ptr() } else { std::ptr::null_mut() },
+                                      if signer.is_some() { voted.as_mut_ptr() } else { std::ptr::null_mut() })
+    };
+    check(rc);
+    (0..m).map(|i| {
+        let mut v = Verdict { code: codes[i] as u32, digest: [0u8; 32], kind: kinds[i] };
+        v.digest.copy_from_slice(&digests[32 * i..32 * i + 32]);
+        let sig = if voted[i] != 0 {
+            let mut s = [0u8; 64];
+            s.copy_from_slice(&sigs[64 * i..64 * i + 64]);
+            Some(s)
+        } else {
+            None
+        };
+        (v, sig)
+    }).collect()
+}
