@@ -66,6 +66,7 @@ struct MsmArgs {
   uint32_t* list;             // votes of the groups that failed (for the exact leaves)
   uint32_t* count;
   uint32_t* stats;            // MSM_ST_* words (nwc_msm_stats, the skip policy)
+  uint32_t adapt;             // 0: the equation on every group, whatever mode an earlier launch left (msm_adapt)
 };
 
 // device-resident MSM statistics and the skip policy's state (u32 words of DevCtx::msm_stats)
@@ -222,7 +223,7 @@ __global__ __launch_bounds__(64, 2) void k_verify_msm(MsmArgs a) {
   int16_t* const rdig = reinterpret_cast<int16_t*>(wbase + (size_t)MSM_NPTS * MSM_POINT_U4 * 16);
   const uint64_t G = a.group;
   const uint64_t ngroups = (a.nv + G - 1) / G;
-  const bool skip = a.stats && a.stats[MSM_ST_MODE] != 0;
+  const bool skip = a.adapt && a.stats && a.stats[MSM_ST_MODE] != 0;
   for (uint64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
     const uint64_t v0 = g * G;
     const u32 ng = (u32)(a.nv - v0 < G ? a.nv - v0 : G);

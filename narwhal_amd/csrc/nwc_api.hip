@@ -1612,12 +1612,16 @@ int launch_msm(DevCtx& d, const uint8_t* dig, const uint32_t* mi, const uint8_t*
   draw_seed(ma.seed);
   ma.comb16 = d.comb16; ma.scratch = d.msm_scratch;
   ma.leaf_words = leaf; ma.list = mlist; ma.count = mcount; ma.stats = d.msm_stats;
+  // the policy off holds for this launch too: a mode an earlier launch armed is not obeyed, and
+  // k_msm_policy clears it below
+  const uint32_t adapt = knobs().msm_adapt.load();
+  ma.adapt = adapt;
   HIP_TRY(hipMemsetAsync(leaf, 0, 8 * ((nvotes + 63) / 64), s));
   HIP_TRY(hipMemsetAsync(mcount, 0, sizeof(uint32_t), s));
   HIP_TRY(hipMemsetAsync(d.fb_count, 0, sizeof(uint32_t), s));
   hipLaunchKernelGGL(nwc::k_verify_msm, dim3((unsigned)grid), dim3(64), 0, s, ma);
   HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(nwc::k_msm_policy, dim3(1), dim3(64), 0, s, d.msm_stats, (uint32_t)knobs().msm_adapt.load());
+  hipLaunchKernelGGL(nwc::k_msm_policy, dim3(1), dim3(64), 0, s, d.msm_stats, adapt);
   HIP_TRY(hipGetLastError());
   const nwc::VerifyArgs a{dig, mi, 0, pks, sigs, leaf, nvotes, 0, d.base_table, d.base24, d.scratch, d.fb_list,
                           d.fb_count, 0u, nwc::Committee{}};

@@ -82,6 +82,13 @@ __device__ __noinline__ u32 torsion_dlog(const ge_p2& P) {
   return j;
 }
 
+// q mod 8 of z k = (z k mod l) + q l, from the low bits of z, k and zk = z k mod l:
+// q = (z k - (z k mod l)) / l and 1/l = 5 mod 8
+__device__ __forceinline__ u32 resolve_q8(const u32 z[4], const u32 k[8], const u32 zk[8]) {
+  const u32 z8 = z[0] & 7u, k8 = k[0] & 7u, r8 = zk[0] & 7u;
+  return (5u * ((z8 * k8 + 8u - r8) & 7u)) & 7u;
+}
+
 __global__ __launch_bounds__(256) void k_vote_resolve(ResolveArgs a) {
   __shared__ ge_niels sB[129];
   const uint32_t count = *a.count;
@@ -152,8 +159,8 @@ __global__ __launch_bounds__(256) void k_vote_resolve(ResolveArgs a) {
       u32 z[4], zk[8];
       straus_z(a.seed, v, z);
       sc_mul128(z, kw, zk);
-      const u32 z8 = z[0] & 7u, k8 = kw[0] & 7u, r8 = zk[0] & 7u;
-      const u32 q8 = (5u * ((z8 * k8 + 8u - r8) & 7u)) & 7u;   // q = (z k - (z k mod l)) / l; 1/l = 5 mod 8
+      const u32 z8 = z[0] & 7u;
+      const u32 q8 = resolve_q8(z, kw, zk);
       const u32 de = torsion_dlog(ge_p3_to_p2(e));
       const u32 dl = torsion_dlog(ge_mul_l(A));
       dl_ok = de < 8 && dl < 8;
