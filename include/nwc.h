@@ -519,6 +519,85 @@ int nwc_dev_sanitize_messages_ex(const void* d_data, const void* d_offsets, uint
                                  const uint8_t* vote_target, void* signer, void* d_codes, void* d_digests32,
                                  void* d_kinds, void* d_vote_sigs, void* d_voted, void* stream);
 
+/* Decoded message views: the batch entries hand back what the device decoded, so that Core does not
+ * deserialise the message a second time.  A view is an index
+ * into the wire bytes the caller still holds plus what the wire does not contain in usable form: the
+ * message's own keys decoded (32 raw bytes and the committee index), a certificate's voters as
+ * committee indices, and the canonical BTreeMap / BTreeSet form of a payload or of parents that did
+ * NOT arrive strictly ascending.  Honest encoders send them ascending: those stay in the wire and the
+ * view gives their offsets.  One fixed record per message (160 bytes, little-endian, 8-byte aligned)
+ * and a small variable part in `body`. */
+#define NWC_VIEW_PAYLOAD_IN_BODY 1
+#define NWC_VIEW_PARENTS_IN_BODY 2
+typedef struct nwc_msg_view {
+  uint8_t decoded;      /* 1 iff the message decoded: every code except SERIALIZATION_ERROR,
+                           UNEXPECTED_MESSAGE and DECODE_PANIC.  0: kind and code are set, all else zero */
+  uint8_t kind;         /* as kinds[i] */
+  uint8_t flags;        /* NWC_VIEW_PAYLOAD_IN_BODY | NWC_VIEW_PARENTS_IN_BODY */
+  uint8_t reserved0;    /* 0 */
+  int32_t code;         /* == codes[i] */
+  uint64_t round;       /* Header.round (certificate: its header's) / Vote.round */
+  uint8_t author[32];   /* decoded key: Header.author / Vote.author */
+  uint8_t origin[32];   /* Vote.origin; zero for headers and certificates */
+  uint8_t id[32];       /* Header.id / Vote.id, as on the wire */
+  int32_t author_index; /* index in the order of the committee configuration's keys, -1 = not a member */
+  int32_t origin_index; /* votes only; -1 otherwise */
+  uint32_t n_payload;   /* canonical counts: after dedupe, a map key keeps its LAST value */
+  uint32_t n_parents;
+  uint32_t n_votes;     /* certificates; 0 otherwise */
+  uint32_t sig_off;     /* byte offset from the message's start of the header's / vote's 64-B signature */
+  uint64_t payload_off; /* IN_BODY: byte offset into body, else offset from the message's start.
+                           n_payload x (32-B digest, u32 LE worker id) */
+  uint64_t parents_off; /* same rule; n_parents x 32 B */
+  uint64_t votes_off;   /* byte offset into body of n_votes x { int32 member_index; uint32 vote_off; }
+                           (0 when n_votes is 0); vote_off = offset from the message's start of the
+                           vote's key string (its u64 length field); the signature follows the string */
+} nwc_msg_view;
+
+/* The bytes of body a call over m messages in `total` wire bytes can use at most: total + 64 m.  (A
+ * message's body holds at most 36 P + 32 Q + 8 V bytes in three 16-byte-aligned areas, less than its
+ * wire length + 64.) */
+uint64_t nwc_msg_view_body_bound(uint64_t total, uint64_t m);
+
+/* nwc_sanitize_messages_ex with the views: the first 13 arguments, codes, digests32, kinds,
+ * vote_sigs and voted are exactly that entry's, byte for byte.  views: m nwc_msg_view records.
+ * With views == NULL the entry IS nwc_sanitize_messages_ex: nothing more is launched or allocated
+ * and body, body_cap and body_used are ignored.  With views, body and body_used are required,
+ * body_cap >= nwc_msg_view_body_bound(offsets[m] - offsets[0], m), and every message is shorter
+ * than 2^32 bytes: a call that breaks one of these returns NWC_ERR_ARG before anything is queued.
+ *
+ * The body's areas come from a bump allocator on the device in 16-byte units: their order is
+ * unspecified, they never overlap, every one starts on a multiple of 16, and *body_used is the
+ * allocator's final value in bytes (<= the bound).  Only the records (160 m bytes) and body_used
+ * bytes of body come back, never body_cap.  On an error < 0 every view is zero and *body_used = 0.
+ * The views are written by one more launch behind the codes (one wave per message), whatever the
+ * number of chunks.
+ *
+ * Devices: a host call that asks for views is not sharded; it runs whole on the calling thread's
+ * device (nwc_dev_set_device), or on the signer's when it carries one.  m == 0 is a no-op returning
+ * 0; NWC_ERR_NOT_INIT before nwc_init and before nwc_set_committee_config.  The sanitizer handle
+ * keeps returning code, digest and kind only. */
+int nwc_sanitize_messages_view(const uint8_t* data, const uint64_t* offsets, size_t m,
+                               const uint64_t* gc_rounds, uint64_t gc_round,
+                               const uint8_t* vote_targets80, const uint8_t* vote_target, void* signer,
+                               int32_t* codes, uint8_t* digests32, uint8_t* kinds,
+                               uint8_t* vote_sigs, uint8_t* voted,
+                               void* views,            /* m nwc_msg_view records, or NULL */
+                               uint8_t* body, size_t body_cap,
+                               uint64_t* body_used);   /* bytes of body in use */
+
+/* Device-resident variant: the arguments of nwc_dev_sanitize_messages_ex, then d_views (device
+ * m x 160 B, 8-byte aligned), d_body (device, 16-byte aligned, body_cap bytes), d_body_used (device
+ * u64); `stream` stays last.  d_views == NULL: nwc_dev_sanitize_messages_ex.  The offsets live on
+ * the device, so a message of 2^32 bytes or more is not refused here: it gets decoded = 0.
+ * Synchronises no more often than the _ex entry; the views, the body and d_body_used are queued on
+ * `stream` behind the codes.  On an error < 0 the views and d_body_used are zeroed on `stream`. */
+int nwc_dev_sanitize_messages_view(const void* d_data, const void* d_offsets, uint64_t m, uint64_t total,
+                                   const void* d_gc_rounds, uint64_t gc_round, const void* d_vote_targets80,
+                                   const uint8_t* vote_target, void* signer, void* d_codes, void* d_digests32,
+                                   void* d_kinds, void* d_vote_sigs, void* d_voted, void* d_views, void* d_body,
+                                   uint64_t body_cap, void* d_body_used, void* stream);
+
 /* ---- digests -------------------------------------------------------------------------- */
 /* Sha512::digest(bytes)[..32] -- worker/src/processor.rs:38 and crypto's `Hash for &[u8]`
  * (crypto/src/tests/crypto_tests.rs:8-12). */

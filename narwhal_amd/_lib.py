@@ -111,6 +111,15 @@ _SIGS = {
                                                     ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, _c_u8p,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                     ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "nwc_msg_view_body_bound": (ctypes.c_uint64, [ctypes.c_uint64, ctypes.c_uint64]),
+    "nwc_sanitize_messages_view": (ctypes.c_int, [_c_u8p, _c_u8p, ctypes.c_size_t, _c_u8p, ctypes.c_uint64, _c_u8p, _c_u8p,
+                                                  ctypes.c_void_p, _c_u8p, _c_u8p, _c_u8p, _c_u8p, _c_u8p,
+                                                  ctypes.c_void_p, _c_u8p, ctypes.c_size_t, ctypes.c_void_p]),
+    "nwc_dev_sanitize_messages_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                      ctypes.c_void_p, ctypes.c_uint64, ctypes.c_void_p, _c_u8p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_uint64, ctypes.c_void_p, ctypes.c_void_p]),
     "nwc_digester_create": (ctypes.c_void_p, [ctypes.c_uint32, ctypes.c_uint32]),
     "nwc_digester_submit": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint64]),
     "nwc_digester_poll": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_void_p,
@@ -139,6 +148,20 @@ class Memory(ctypes.Structure):
 
     def as_dict(self):
         return {name: int(getattr(self, name)) for name, _ in self._fields_}
+
+
+VIEW_PAYLOAD_IN_BODY = 1
+VIEW_PARENTS_IN_BODY = 2
+
+
+class MsgView(ctypes.Structure):
+    """nwc_msg_view (include/nwc.h): the 160-byte record of nwc_sanitize_messages_view."""
+    _fields_ = [("decoded", ctypes.c_uint8), ("kind", ctypes.c_uint8), ("flags", ctypes.c_uint8),
+                ("reserved0", ctypes.c_uint8), ("code", ctypes.c_int32), ("round", ctypes.c_uint64),
+                ("author", ctypes.c_uint8 * 32), ("origin", ctypes.c_uint8 * 32), ("id", ctypes.c_uint8 * 32),
+                ("author_index", ctypes.c_int32), ("origin_index", ctypes.c_int32), ("n_payload", ctypes.c_uint32),
+                ("n_parents", ctypes.c_uint32), ("n_votes", ctypes.c_uint32), ("sig_off", ctypes.c_uint32),
+                ("payload_off", ctypes.c_uint64), ("parents_off", ctypes.c_uint64), ("votes_off", ctypes.c_uint64)]
 
 
 def memory_info() -> dict:

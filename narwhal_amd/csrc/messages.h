@@ -737,6 +737,169 @@ __global__ __launch_bounds__(256) void k_msg_kinds(const uint32_t* __restrict__ 
   if (i < m) kinds[i] = (uint8_t)(rec[4 * i] & 255u);
 }
 
+// ---- decoded message views (nwc_sanitize_messages_view) --------------------------
+// What the parse decoded, handed to the caller as an index into the wire bytes it still holds: one
+// 160-byte record per message (nwc_msg_view of include/nwc.h, as 40 little-endian words) plus a
+// small variable part in `body`.  Payload and parents that arrive strictly ascending -- what an
+// honest encoder sends -- stay in the wire and the record gives their offsets; only other input is
+// rewritten in canonical form into the body.  A certificate's voters go to the body as
+// (committee index, offset of the vote in the message) pairs.
+struct ViewOut {
+  uint32_t* views;                 // m x VIEW_WORDS
+  uint8_t* body;                   // 16-byte aligned
+  uint64_t body_cap;               // bytes
+  unsigned long long* body_used;   // the bump allocator (bytes, a multiple of 16), zero at the launch
+};
+constexpr int VIEW_WORDS = 40;
+enum ViewFlag : u32 { VIEW_PAYLOAD_IN_BODY = 1, VIEW_PARENTS_IN_BODY = 2 };
+
+// cnt wire entries of REC bytes at `src`, digests first: strictly ascending?  (Every lane calls.)
+template <uint64_t REC>
+__device__ __forceinline__ bool wire_ascending(const uint8_t* base, uint64_t src, uint64_t cnt, u32 lane) {
+  bool asc = true;
+  for (uint64_t e = lane; e + 1 < cnt; e += 64) {
+    u32 x[8], y[8];
+    ld_words<8>(base, src + REC * e, x);
+    ld_words<8>(base, src + REC * (e + 1), y);
+    asc = asc && dig_cmp(x, y) < 0;
+  }
+  return __all(asc);
+}
+
+// One wave per message of the call, after k_finalize_messages (the codes are final; rec, rec_n, the
+// vote slots and the hashbuf slots are the parses').  Every exit is block-uniform: the records, the
+// codes and every wire field read here are the same in all lanes.  A message that did not decode --
+// or, which cannot happen, whose body areas would not fit -- gets decoded = 0 with its kind and code.
+__global__ __launch_bounds__(64) void k_message_views(MsgArgs a, Committee cm, const int32_t* __restrict__ codes, ViewOut o) {
+  const uint64_t i = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= a.m) return;   // block-uniform, as every exit below
+  const u32 r0 = a.rec[4 * i], kind = r0 & 255u;
+  const uint64_t beg = a.offsets[i], end = a.offsets[i + 1];
+  u32 w[VIEW_WORDS];
+  _Pragma("unroll") for (int k = 0; k < VIEW_WORDS; ++k) w[k] = 0;
+  bool ok = kind != MSG_OTHER && !(r0 & MF_PARSE_ERR) && ((end - beg) >> 32) == 0;
+  u32 flags = 0;
+  if (ok && kind == MSG_VOTE) {
+    MsgReader r{a.data, beg + 4, end, true, false};
+    u32 id[8], origin[8], author[8];
+    r.bytes32(id);
+    const uint64_t round = r.u64();
+    r.key(origin);
+    r.key(author);
+    const uint64_t sig_off = r.pos - beg;
+    r.need(64);
+    ok = r.ok;
+    w[2] = (u32)round;
+    w[3] = (u32)(round >> 32);
+    _Pragma("unroll") for (int k = 0; k < 8; ++k) { w[4 + k] = author[k]; w[12 + k] = origin[k]; w[20 + k] = id[k]; }
+    w[28] = (u32)committee_lookup(cm, author);
+    w[29] = (u32)committee_lookup(cm, origin);
+    w[33] = (u32)sig_off;
+  } else if (ok) {
+    MsgReader r{a.data, beg + 4, end, true, false};
+    u32 author[8], id[8];
+    r.key(author);
+    const uint64_t round = r.u64();
+    const uint64_t P = r.u64();
+    r.need(P <= (1ull << 40) ? P * 36 : ~0ull);
+    const uint64_t pay_off = r.pos;
+    if (r.ok) r.pos += P * 36;
+    const uint64_t Q = r.u64();
+    r.need(Q <= (1ull << 40) ? Q * 32 : ~0ull);
+    const uint64_t par_off = r.pos;
+    if (r.ok) r.pos += Q * 32;
+    r.bytes32(id);
+    const uint64_t sig_off = r.pos - beg;
+    r.need(64);
+    if (r.ok) r.pos += 64;
+    uint64_t V = 0, votes_off = r.pos;
+    bool fast = false;
+    if (kind == MSG_CERTIFICATE) {
+      V = r.u64();
+      votes_off = r.pos;
+      // the parse's own test of its fast path: the voff[] entries exist only when it fails
+      fast = r.ok && V <= (r.end - r.pos) / 116;
+      if (fast) {
+        bool f = true;
+        for (uint64_t v = lane; v < V; v += 64) f = f && ld_u64(r.base, votes_off + 116 * v) == 44;
+        fast = __all(f);
+      }
+      ok = r.ok && V == a.rec_n[i];
+    } else {
+      ok = r.ok;
+    }
+    if (ok) {   // block-uniform
+      const bool asc_p = wire_ascending<36>(r.base, pay_off, P, lane);
+      const bool asc_q = wire_ascending<32>(r.base, par_off, Q, lane);
+      // three 16-byte-aligned areas from one bump of the allocator; a non-canonical sequence gets
+      // its wire count's room (canon_entries sorts in place)
+      const uint64_t need_p = asc_p ? 0 : (36 * P + 15) & ~(uint64_t)15;
+      const uint64_t need_q = asc_q ? 0 : (32 * Q + 15) & ~(uint64_t)15;
+      const uint64_t need_v = (8 * V + 15) & ~(uint64_t)15;
+      const uint64_t need = need_p + need_q + need_v;
+      uint64_t at = 0;
+      if (need) {
+        unsigned long long got = 0;
+        if (lane == 0) got = atomicAdd(o.body_used, (unsigned long long)need);
+        at = shfl_u64(got, 0);
+        ok = at <= o.body_cap && need <= o.body_cap - at;
+      }
+      if (ok) {   // block-uniform
+        uint64_t Pc = P, Qc = Q;
+        uint64_t p_at = pay_off - beg, q_at = par_off - beg;
+        if (!asc_p) {
+          p_at = at;
+          Pc = canon_entries<9, true>(r.base, pay_off, P, reinterpret_cast<u32*>(o.body + p_at), lane);
+          flags |= VIEW_PAYLOAD_IN_BODY;
+        }
+        if (!asc_q) {
+          q_at = at + need_p;
+          Qc = canon_entries<8, false>(r.base, par_off, Q, reinterpret_cast<u32*>(o.body + q_at), lane);
+          flags |= VIEW_PARENTS_IN_BODY;
+        }
+        const uint64_t v_at = V ? at + need_p + need_q : 0;
+        if (V) {
+          const u32 vbase = a.rec[4 * i + 2];
+          const u32* voff = reinterpret_cast<const u32*>(a.hashbuf + ((beg + 127) & ~(uint64_t)127) + 128 * i) + 12 + 9 * P + 8 * Q;
+          uint2* out = reinterpret_cast<uint2*>(o.body + v_at);
+          const u32 rel = (u32)(votes_off - beg);
+          for (uint64_t v = lane; v < V; v += 64) {
+            u32 key[8];
+            load_words8(a.v_pk + 32 * ((uint64_t)vbase + v), key);
+            out[v] = make_uint2((u32)committee_lookup(cm, key), rel + (fast ? (u32)(116 * v) : voff[v]));
+          }
+        }
+        w[2] = (u32)round;
+        w[3] = (u32)(round >> 32);
+        _Pragma("unroll") for (int k = 0; k < 8; ++k) { w[4 + k] = author[k]; w[20 + k] = id[k]; }
+        w[28] = (u32)committee_lookup(cm, author);
+        w[29] = 0xFFFFFFFFu;
+        w[30] = (u32)Pc;
+        w[31] = (u32)Qc;
+        w[32] = (u32)V;
+        w[33] = (u32)sig_off;
+        w[34] = (u32)p_at;
+        w[35] = (u32)(p_at >> 32);
+        w[36] = (u32)q_at;
+        w[37] = (u32)(q_at >> 32);
+        w[38] = (u32)v_at;
+        w[39] = (u32)(v_at >> 32);
+      }
+    }
+  }
+  if (!ok) {
+    _Pragma("unroll") for (int k = 2; k < VIEW_WORDS; ++k) w[k] = 0;
+    flags = 0;
+  }
+  w[0] = (ok ? 1u : 0u) | (kind << 8) | (flags << 16);
+  w[1] = (u32)codes[i];
+  // lane k stores word k: one contiguous run of dwords per record
+  u32 mine = 0;
+  _Pragma("unroll") for (int k = 0; k < VIEW_WORDS; ++k) mine = lane == (u32)k ? w[k] : mine;
+  if (lane < (u32)VIEW_WORDS) o.views[VIEW_WORDS * i + lane] = mine;
+}
+
 // Header::digest of the gathered input, one lane per message (a header of 67 parents is 18 blocks)
 __device__ __forceinline__ void header_digest_one(const MsgArgs& a, const uint64_t i) {
   const u32 r0 = a.rec[4 * i], kind = r0 & 255u;

@@ -77,15 +77,23 @@ struct ArenaWalk {
 // padding, their offsets, and the codes, records and digests on their way back.  What
 // nwc_sanitize_messages_ex adds lies behind them, so a call without it keeps the layout above:
 // with own_state the per-message gc_rounds (u64) and vote targets (80 B, SanGroupBuf's record), with
-// votes the Vote::new signatures (64 B) and the "voted" bytes on their way back.
+// votes the Vote::new signatures (64 B) and the "voted" bytes on their way back; with views
+// (nwc_sanitize_messages_view) the view records (MSG_VIEW_BYTES each), the body of
+// view_body_bound(total, m) bytes and the body allocator's counter, behind all of those.
 struct CallArena {
   size_t data, offsets, codes, rec, digests;
   size_t gc_rounds, targets;      // own_state only
   size_t vote_sigs, voted;        // votes only
+  size_t views, body, body_used;  // views only
   size_t bytes;
 };
 constexpr size_t MSG_TARGET_STRIDE = 80;
-inline CallArena call_arena(size_t m, uint64_t total, bool own_state = false, bool votes = false) {
+constexpr size_t MSG_VIEW_BYTES = 160;
+// What the body of a view call can hold at most: per message 36 P + 32 Q + 8 V bytes in three
+// 16-byte-aligned areas (<= 45 bytes of alignment), less than its wire length + 64 (a header's fixed
+// fields alone take more than 160 bytes, a payload entry 36, a parent 32 and a vote >= 72).
+inline uint64_t view_body_bound(uint64_t total, uint64_t m) { return total + 64 * m; }
+inline CallArena call_arena(size_t m, uint64_t total, bool own_state = false, bool votes = false, bool views = false) {
   ArenaWalk w;
   CallArena a{};
   a.data = w.take(total + 16);
@@ -100,6 +108,11 @@ inline CallArena call_arena(size_t m, uint64_t total, bool own_state = false, bo
   if (votes) {
     a.vote_sigs = w.take(64 * m);
     a.voted = w.take(m);
+  }
+  if (views) {
+    a.views = w.take(MSG_VIEW_BYTES * m);
+    a.body = w.take(view_body_bound(total, m));
+    a.body_used = w.take(8);
   }
   a.bytes = w.off;
   return a;

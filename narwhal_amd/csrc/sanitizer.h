@@ -73,6 +73,8 @@ class ChunkFeed {
 // and targets (80-byte records, MSG_TARGET_STRIDE) give message i its own Core state; key is the
 // signer's key record, and with it vote_sigs (m x 64 B) and voted (m bytes) are written by
 // k_vote_msgs behind the codes; kinds (m bytes) is the device entry's twin of the host's kinds.
+// views (m x 160 B, nwc_msg_view), body (16-byte aligned, body_cap bytes) and body_used (u64) are
+// what the _view entries add: k_message_views writes them behind the codes, once per call.
 struct MsgEx {
   const uint64_t* gc_rounds = nullptr;
   const uint8_t* targets = nullptr;
@@ -80,6 +82,10 @@ struct MsgEx {
   uint8_t* vote_sigs = nullptr;
   uint8_t* voted = nullptr;
   uint8_t* kinds = nullptr;
+  uint8_t* views = nullptr;
+  uint8_t* body = nullptr;
+  uint64_t body_cap = 0;
+  uint64_t* body_used = nullptr;
 };
 
 // Device part of nwc_sanitize_messages: messages in HBM (ddata 4-byte aligned with >= 16 bytes
@@ -404,6 +410,14 @@ struct MsgPipeline {
       hipLaunchKernelGGL(nwc::k_msg_kinds, dim3((unsigned)((a.m + 255) / 256)), dim3(256), 0, s, a.rec, (uint64_t)a.m, ex.kinds);
       HIP_TRY(hipGetLastError());
     }
+    if (ex.views) {
+      // the decoded views, once, over the whole call: one wave per message, the body's allocator from zero
+      HIP_TRY(hipMemsetAsync(ex.body_used, 0, 8, s));
+      const nwc::ViewOut vo{reinterpret_cast<uint32_t*>(ex.views), ex.body, ex.body_cap,
+                            reinterpret_cast<unsigned long long*>(ex.body_used)};
+      hipLaunchKernelGGL(nwc::k_message_views, dim3((unsigned)a.m), dim3(64), 0, s, a, cm, (const int32_t*)dcodes, vo);
+      HIP_TRY(hipGetLastError());
+    }
     mark("final queued");
     if (timing && nch > 1) {
       std::string line;
@@ -430,6 +444,11 @@ struct HostEx {
   const nwc::SignKey* key = nullptr;
   uint8_t* vote_sigs = nullptr;
   uint8_t* voted = nullptr;
+  // nwc_sanitize_messages_view: the records (m x 160 B), then the used part of the body, come back
+  // behind the codes
+  uint8_t* views = nullptr;
+  uint8_t* body = nullptr;
+  uint64_t* body_used = nullptr;
 };
 
 // One device's share of a host call: stages the messages (small batches in one copy, large ones
@@ -445,7 +464,7 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
   if (!d.cc_stakes) return set_err(NWC_ERR_NOT_INIT, "nwc_set_committee_config has not been called");
   // staging area (the arena): message bytes, offsets, codes, records, digests
   const bool own_state = hx.gc_rounds || hx.targets;
-  const nwc::plan::CallArena L = nwc::plan::call_arena(m, total, own_state, hx.key != nullptr);
+  const nwc::plan::CallArena L = nwc::plan::call_arena(m, total, own_state, hx.key != nullptr, hx.views != nullptr);
   if (int rc = d.ensure_arena(L.bytes)) return rc;
   if (hx.key)
     if (int rc = ensure_sign_table(d)) return rc;
@@ -460,6 +479,12 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
   if (hx.key) {
     ex.vote_sigs = arena_at<uint8_t>(arena, L.vote_sigs);
     ex.voted = arena_at<uint8_t>(arena, L.voted);
+  }
+  if (hx.views) {
+    ex.views = arena_at<uint8_t>(arena, L.views);
+    ex.body = arena_at<uint8_t>(arena, L.body);
+    ex.body_cap = nwc::plan::view_body_bound(total, m);
+    ex.body_used = arena_at<uint64_t>(arena, L.body_used);
   }
   std::vector<uint64_t> hoff(m + 1);
   for (size_t i = 0; i <= m; ++i) hoff[i] = offsets[i] - base;
@@ -529,9 +554,19 @@ int sanitize_range(int di, const uint8_t* data, const uint64_t* offsets, size_t 
     HIP_TRY(hipMemcpyAsync(hx.vote_sigs, ex.vote_sigs, 64 * m, hipMemcpyDeviceToHost, d.stream));
     HIP_TRY(hipMemcpyAsync(hx.voted, ex.voted, m, hipMemcpyDeviceToHost, d.stream));
   }
+  if (hx.views) {
+    HIP_TRY(hipMemcpyAsync(hx.views, ex.views, nwc::plan::MSG_VIEW_BYTES * m, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipMemcpyAsync(hx.body_used, ex.body_used, 8, hipMemcpyDeviceToHost, d.stream));
+  }
   HIP_TRY(hipStreamSynchronize(d.stream));
   if (kinds)
     for (size_t i = 0; i < m; ++i) kinds[i] = (uint8_t)rec[4 * i];
+  if (hx.views && *hx.body_used) {
+    // only what the allocator handed out, never the whole capacity
+    const uint64_t used = std::min<uint64_t>(*hx.body_used, ex.body_cap);
+    HIP_TRY(hipMemcpyAsync(hx.body, ex.body, used, hipMemcpyDeviceToHost, d.stream));
+    HIP_TRY(hipStreamSynchronize(d.stream));
+  }
   return 0;
 }
 
@@ -641,6 +676,120 @@ int nwc_dev_sanitize_messages_ex(const void* d_data, const void* d_offsets, uint
   ex.gc_rounds = static_cast<const uint64_t*>(d_gc_rounds);
   ex.targets = static_cast<const uint8_t*>(d_vote_targets80);
   ex.kinds = static_cast<uint8_t*>(d_kinds);
+  if (signer) {
+    Signer& sg = *static_cast<Signer*>(signer);
+    if (!sg.d || !sg.key) return fail(set_err(NWC_ERR_NOT_INIT, "the signer's device context was shut down"));
+    if (sg.d != &d) return fail(set_err(NWC_ERR_ARG, "the signer lives on another device than the calling thread's"));
+    if (int rc = ensure_sign_table(d)) return fail(rc);
+    ex.key = sg.key;
+    ex.vote_sigs = static_cast<uint8_t*>(d_vote_sigs);
+    ex.voted = static_cast<uint8_t*>(d_voted);
+  }
+  const int rc = sanitize_dev(d, static_cast<const uint8_t*>(d_data), static_cast<const uint64_t*>(d_offsets), m, total,
+                              {0, (size_t)m}, gc_round, vote_target, static_cast<int32_t*>(d_codes),
+                              static_cast<uint8_t*>(d_digests32), nullptr, s, nullptr, ex);
+  return rc < 0 ? fail(rc) : rc;
+}
+
+uint64_t nwc_msg_view_body_bound(uint64_t total, uint64_t m) { return nwc::plan::view_body_bound(total, m); }
+
+int nwc_sanitize_messages_view(const uint8_t* data, const uint64_t* offsets, size_t m, const uint64_t* gc_rounds,
+                               uint64_t gc_round, const uint8_t* vote_targets80, const uint8_t* vote_target, void* signer,
+                               int32_t* codes, uint8_t* digests32, uint8_t* kinds, uint8_t* vote_sigs, uint8_t* voted,
+                               void* views, uint8_t* body, size_t body_cap, uint64_t* body_used) {
+  if (!views)
+    return nwc_sanitize_messages_ex(data, offsets, m, gc_rounds, gc_round, vote_targets80, vote_target, signer, codes, digests32,
+                                    kinds, vote_sigs, voted);
+  // on an error < 0 every view and every vote output is zero, and no body byte is in use
+  auto fail = [&](int rc) {
+    if (m) std::memset(views, 0, nwc::plan::MSG_VIEW_BYTES * m);
+    if (m && body_used) *body_used = 0;
+    if (signer && m && vote_sigs) std::memset(vote_sigs, 0, 64 * m);
+    if (signer && m && voted) std::memset(voted, 0, m);
+    return rc;
+  };
+  if (signer && (!vote_sigs || !voted)) return fail(set_err(NWC_ERR_ARG, "a signer needs vote_sigs and voted"));
+  if (m == 0) return 0;
+  // the argument rules first: nothing is queued for a call that breaks one
+  if (!body || !body_used) return fail(set_err(NWC_ERR_ARG, "views need body and body_used"));
+  if (!data || !offsets || !codes) return fail(set_err(NWC_ERR_ARG, "null buffer"));
+  for (size_t i = 0; i < m; ++i) {
+    if (offsets[i + 1] < offsets[i]) return fail(set_err(NWC_ERR_ARG, "offsets not monotone at %zu", i));
+    if ((offsets[i + 1] - offsets[i]) >> 32) return fail(set_err(NWC_ERR_ARG, "message %zu is 2^32 bytes or longer", i));
+  }
+  if (body_cap < nwc::plan::view_body_bound(offsets[m] - offsets[0], m))
+    return fail(set_err(NWC_ERR_ARG, "body_cap is below nwc_msg_view_body_bound(total, m)"));
+  if (int rc = require_init()) return fail(rc);
+  HostEx hx;
+  hx.gc_rounds = gc_rounds;
+  hx.targets = vote_targets80;
+  hx.views = static_cast<uint8_t*>(views);
+  hx.body = body;
+  hx.body_used = body_used;
+  // not sharded: whole on the signer's device, or on the calling thread's
+  int di = t_dev < (int)g_devs.size() ? t_dev : 0;
+  if (signer) {
+    Signer& sg = *static_cast<Signer*>(signer);
+    if (!sg.d || !sg.key) return fail(set_err(NWC_ERR_NOT_INIT, "the signer's device context was shut down"));
+    di = -1;
+    for (size_t k = 0; k < g_devs.size(); ++k)
+      if (g_devs[k].get() == sg.d) di = (int)k;
+    if (di < 0) return fail(set_err(NWC_ERR_ARG, "the signer's device is not initialised"));
+    hx.key = sg.key;
+    hx.vote_sigs = vote_sigs;
+    hx.voted = voted;
+  }
+  const int rc = sanitize_range(di, data, offsets, m, gc_round, vote_target, codes, digests32, kinds, hx);
+  return rc < 0 ? fail(rc) : rc;
+}
+
+int nwc_dev_sanitize_messages_view(const void* d_data, const void* d_offsets, uint64_t m, uint64_t total,
+                                   const void* d_gc_rounds, uint64_t gc_round, const void* d_vote_targets80,
+                                   const uint8_t* vote_target, void* signer, void* d_codes, void* d_digests32, void* d_kinds,
+                                   void* d_vote_sigs, void* d_voted, void* d_views, void* d_body, uint64_t body_cap,
+                                   void* d_body_used, void* stream) {
+  if (!d_views)
+    return nwc_dev_sanitize_messages_ex(d_data, d_offsets, m, total, d_gc_rounds, gc_round, d_vote_targets80, vote_target, signer,
+                                        d_codes, d_digests32, d_kinds, d_vote_sigs, d_voted, stream);
+  if (signer && (!d_vote_sigs || !d_voted)) return set_err(NWC_ERR_ARG, "a signer needs d_vote_sigs and d_voted");
+  if (m == 0) return 0;
+  if (!d_body || !d_body_used) return set_err(NWC_ERR_ARG, "d_views needs d_body and d_body_used");
+  if ((reinterpret_cast<uintptr_t>(d_views) & 7) || (reinterpret_cast<uintptr_t>(d_body) & 15) ||
+      (reinterpret_cast<uintptr_t>(d_body_used) & 7))
+    return set_err(NWC_ERR_ARG, "d_views and d_body_used must be 8-byte and d_body 16-byte aligned");
+  if (body_cap < nwc::plan::view_body_bound(total, m))
+    return set_err(NWC_ERR_ARG, "body_cap is below nwc_msg_view_body_bound(total, m)");
+  if (int rc = require_init()) return rc;
+  DevCtx& d = *ctx(t_dev < (int)g_devs.size() ? t_dev : 0);
+  std::lock_guard<std::mutex> lk(d.mu);
+  HIP_TRY(hipSetDevice(d.hip_id));
+  const hipStream_t s = stream ? static_cast<hipStream_t>(stream) : d.stream;
+  // on an error < 0 every view and every vote output is zero and no body byte is in use (queued on
+  // the call's stream)
+  auto fail = [&](int rc) {
+    (void)hipMemsetAsync(d_views, 0, nwc::plan::MSG_VIEW_BYTES * m, s);
+    (void)hipMemsetAsync(d_body_used, 0, 8, s);
+    if (signer) {
+      (void)hipMemsetAsync(d_vote_sigs, 0, 64 * m, s);
+      (void)hipMemsetAsync(d_voted, 0, m, s);
+    }
+    return rc;
+  };
+  if (!d_data || !d_offsets || !d_codes) return fail(set_err(NWC_ERR_ARG, "null buffer"));
+  if ((reinterpret_cast<uintptr_t>(d_data) & 3) != 0) return fail(set_err(NWC_ERR_ARG, "d_data must be 4-byte aligned"));
+  if ((reinterpret_cast<uintptr_t>(d_gc_rounds) & 7) || (reinterpret_cast<uintptr_t>(d_vote_targets80) & 3))
+    return fail(set_err(NWC_ERR_ARG, "d_gc_rounds must be 8-byte and d_vote_targets80 4-byte aligned"));
+  if (signer && ((reinterpret_cast<uintptr_t>(d_vote_sigs) & 3) || (reinterpret_cast<uintptr_t>(d_digests32) & 15)))
+    return fail(set_err(NWC_ERR_ARG, "with a signer d_vote_sigs must be 4-byte and d_digests32 16-byte aligned"));
+  if (!d.cc_stakes) return fail(set_err(NWC_ERR_NOT_INIT, "nwc_set_committee_config has not been called"));
+  MsgEx ex;
+  ex.gc_rounds = static_cast<const uint64_t*>(d_gc_rounds);
+  ex.targets = static_cast<const uint8_t*>(d_vote_targets80);
+  ex.kinds = static_cast<uint8_t*>(d_kinds);
+  ex.views = static_cast<uint8_t*>(d_views);
+  ex.body = static_cast<uint8_t*>(d_body);
+  ex.body_cap = body_cap;
+  ex.body_used = static_cast<uint64_t*>(d_body_used);
   if (signer) {
     Signer& sg = *static_cast<Signer*>(signer);
     if (!sg.d || !sg.key) return fail(set_err(NWC_ERR_NOT_INIT, "the signer's device context was shut down"));

@@ -12,12 +12,15 @@ Certificate digests, committee checks and all signatures on the device).
   sanitize_many(messages, committee, gc_round, current_header) -> [DagError | None]
   sanitize_many_ex(messages, committee, states, gc_round, target, signer)
                                      -> [(DagError | None, Digest, kind, Signature | None)]
+  sanitize_many_view(...)            the same, plus the Header / Vote / Certificate of every message
+                                     that decoded, built from the device's view of it and the wire
 Wire format = bincode of `PrimaryMessage` (primary/src/primary.rs:33-38), built by `to_bytes()`.
 The object-level `verify` / `digest` calls go through the same GPU batch path (a batch of one);
 there is no CPU verification path.
 """
 from __future__ import annotations
 
+import base64
 import ctypes
 import struct
 from dataclasses import dataclass, field
@@ -27,7 +30,7 @@ from . import _lib
 from .crypto import Digest, PublicKey, SecretKey, Signature, Signer, digest_bytes
 
 __all__ = ["DagError", "Authority", "Committee", "Header", "Vote", "Certificate", "sanitize_many",
-           "sanitize_many_ex", "Sanitizer", "DAG_ERRORS"]
+           "sanitize_many_ex", "sanitize_many_view", "Sanitizer", "DAG_ERRORS"]
 
 DAG_ERRORS = ["Ok", "InvalidSignature", "InvalidHeaderId", "MalformedHeader", "UnknownAuthority",
               "AuthorityReuse", "CertificateRequiresQuorum", "TooOld", "SerializationError", "UnexpectedVote",
@@ -358,3 +361,78 @@ def sanitize_many_ex(messages: Sequence[bytes], committee: Committee,
     sraw, vraw = (sigs.raw, voted.raw) if signer is not None else (b"", bytes(m))
     return [(None if codes[i] == 0 else DagError(codes[i]), Digest(raw[32 * i:32 * i + 32]), kraw[i],
              Signature.from_bytes(sraw[64 * i:64 * i + 64]) if vraw[i] else None) for i in range(m)]
+
+
+def _view_objects(v: "_lib.MsgView", wire: bytes, body: bytes, keys: List[PublicKey]):
+    """Header / Vote / Certificate of one decoded message from its view, the wire and the body."""
+    sig = Signature.from_bytes(wire[v.sig_off:v.sig_off + 64])
+    if v.kind == 1:
+        return Vote(Digest(bytes(v.id)), int(v.round), PublicKey(bytes(v.origin)), PublicKey(bytes(v.author)), sig)
+    src, at = (body, v.payload_off) if v.flags & _lib.VIEW_PAYLOAD_IN_BODY else (wire, v.payload_off)
+    payload = {Digest(src[at + 36 * e:at + 36 * e + 32]): struct.unpack_from("<I", src, at + 36 * e + 32)[0]
+               for e in range(v.n_payload)}
+    src, at = (body, v.parents_off) if v.flags & _lib.VIEW_PARENTS_IN_BODY else (wire, v.parents_off)
+    parents = {Digest(src[at + 32 * e:at + 32 * e + 32]) for e in range(v.n_parents)}
+    header = Header(PublicKey(bytes(v.author)), int(v.round), payload, parents, Digest(bytes(v.id)), sig)
+    if v.kind == 0:
+        return header
+    votes = []
+    for e in range(v.n_votes):
+        k, off = struct.unpack_from("<iI", body, v.votes_off + 8 * e)
+        n = struct.unpack_from("<Q", wire, off)[0]
+        if k >= 0:
+            key = keys[k]
+        else:
+            # a voter outside the committee: the key is the first 32 bytes its text encodes (the
+            # device has accepted the text: 43 symbols of the alphabet come first)
+            key = PublicKey(base64.b64decode(wire[off + 8:off + 8 + 43] + b"=")[:32])
+        votes.append((key, Signature.from_bytes(wire[off + 8 + n:off + 8 + n + 64])))
+    return Certificate(header, votes)
+
+
+def sanitize_many_view(messages: Sequence[bytes], committee: Committee,
+                       states: Optional[Sequence[Tuple[int, Optional[Header]]]] = None, gc_round: int = 0,
+                       target: Optional[Header] = None, signer: Optional[Signer] = None) -> List[tuple]:
+    """`sanitize_many_ex` that also hands back what the device decoded (nwc_sanitize_messages_view).
+    Returns per message (DagError or None, digest, kind, Signature or None, object): `object` is the
+    Header / Vote / Certificate of a message that decoded -- whatever its verdict -- built from its
+    view and the wire bytes alone, and None for one that did not (SerializationError,
+    UnexpectedMessage, DecodePanic).  Nothing is decoded on the host: fields come from the record,
+    payload and parents from the wire or the body at the offsets the record names, voters from the
+    committee by index (only a voter outside the committee has its key text read)."""
+    lib = _lib.load()
+    committee.install()
+    m = len(messages)
+    if m == 0:
+        return []
+    if states is not None and len(states) != m:
+        raise ValueError("states: one (gc_round, current header) per message")
+    offs = [0]
+    for b in messages:
+        offs.append(offs[-1] + len(b))
+    data = b"".join(messages) or b"\0"
+    offsets = (ctypes.c_uint64 * (m + 1))(*offs)
+    codes = (ctypes.c_int32 * m)()
+    dig = ctypes.create_string_buffer(32 * m)
+    kinds = ctypes.create_string_buffer(m)
+    gcs = recs = None
+    if states is not None:
+        gcs = (ctypes.c_uint64 * m)(*[int(s[0]) for s in states])
+        recs = b"".join(bytes(80) if s[1] is None else _target72(s[1]) + b"\x01" + bytes(7) for s in states)
+    sigs = ctypes.create_string_buffer(64 * m) if signer is not None else None
+    voted = ctypes.create_string_buffer(m) if signer is not None else None
+    views = (_lib.MsgView * m)()
+    cap = int(lib.nwc_msg_view_body_bound(offs[-1], m))
+    body = ctypes.create_string_buffer(cap)
+    used = ctypes.c_uint64(0)
+    t = _target72(target)
+    _lib.check(lib.nwc_sanitize_messages_view(_lib.buf(data), offsets, m, gcs, gc_round, _lib.buf(recs) if recs else None,
+                                              _lib.buf(t) if t else None, signer.handle if signer is not None else None,
+                                              codes, dig, kinds, sigs, voted, views, body, cap, ctypes.byref(used)))
+    raw, kraw = dig.raw, kinds.raw
+    sraw, vraw = (sigs.raw, voted.raw) if signer is not None else (b"", bytes(m))
+    braw = body.raw[:used.value]
+    keys = list(committee.authorities)
+    return [(None if codes[i] == 0 else DagError(codes[i]), Digest(raw[32 * i:32 * i + 32]), kraw[i],
+             Signature.from_bytes(sraw[64 * i:64 * i + 64]) if vraw[i] else None,
+             _view_objects(views[i], bytes(messages[i]), braw, keys) if views[i].decoded else None) for i in range(m)]

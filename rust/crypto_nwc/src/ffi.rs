@@ -21,6 +21,33 @@ pub struct nwc_memory {
     pub device_total: u64,
 }
 
+/// One decoded message of `nwc_sanitize_messages_view` (160 bytes; include/nwc.h).
+#[allow(non_camel_case_types)]
+#[repr(C)]
+#[derive(Debug, Clone, Copy)]
+pub struct nwc_msg_view {
+    pub decoded: u8,
+    pub kind: u8,
+    pub flags: u8,
+    pub reserved0: u8,
+    pub code: i32,
+    pub round: u64,
+    pub author: [u8; 32],
+    pub origin: [u8; 32],
+    pub id: [u8; 32],
+    pub author_index: i32,
+    pub origin_index: i32,
+    pub n_payload: u32,
+    pub n_parents: u32,
+    pub n_votes: u32,
+    pub sig_off: u32,
+    pub payload_off: u64,
+    pub parents_off: u64,
+    pub votes_off: u64,
+}
+pub const NWC_VIEW_PAYLOAD_IN_BODY: u8 = 1;
+pub const NWC_VIEW_PARENTS_IN_BODY: u8 = 2;
+
 #[link(name = "nwc")]
 extern "C" {
     pub fn nwc_init(device_mask: u32) -> c_int;
@@ -99,6 +126,19 @@ extern "C" {
                                         vote_target: *const u8, signer: *mut c_void, d_codes: *mut c_void,
                                         d_digests32: *mut c_void, d_kinds: *mut c_void, d_vote_sigs: *mut c_void,
                                         d_voted: *mut c_void, stream: *mut c_void) -> c_int;
+    pub fn nwc_msg_view_body_bound(total: u64, m: u64) -> u64;
+    /// `views`: m `nwc_msg_view` records (or null: `nwc_sanitize_messages_ex`).
+    pub fn nwc_sanitize_messages_view(data: *const u8, offsets: *const u64, m: usize, gc_rounds: *const u64, gc_round: u64,
+                                      vote_targets80: *const u8, vote_target: *const u8, signer: *mut c_void,
+                                      codes: *mut i32, digests32: *mut u8, kinds: *mut u8, vote_sigs: *mut u8,
+                                      voted: *mut u8, views: *mut c_void, body: *mut u8, body_cap: usize,
+                                      body_used: *mut u64) -> c_int;
+    pub fn nwc_dev_sanitize_messages_view(d_data: *const c_void, d_offsets: *const c_void, m: u64, total: u64,
+                                          d_gc_rounds: *const c_void, gc_round: u64, d_vote_targets80: *const c_void,
+                                          vote_target: *const u8, signer: *mut c_void, d_codes: *mut c_void,
+                                          d_digests32: *mut c_void, d_kinds: *mut c_void, d_vote_sigs: *mut c_void,
+                                          d_voted: *mut c_void, d_views: *mut c_void, d_body: *mut c_void, body_cap: u64,
+                                          d_body_used: *mut c_void, stream: *mut c_void) -> c_int;
 
     pub fn nwc_digest32(data: *const u8, len: usize, out32: *mut u8) -> c_int;
     pub fn nwc_sha512_trunc32_many(data: *const u8, offsets: *const u64, n: usize, out32: *mut u8) -> c_int;

@@ -497,3 +497,136 @@ pub fn sanitize_batch(wires: &[&[u8]], states: &[FrameState], signer: Option<&Si
         (v, sig)
     }).collect()
 }
+
+pub use ffi::nwc_msg_view as MsgView;
+
+/// The views of one `sanitize_batch_view` call: a record per message and the body they share.
+pub struct BatchViews {
+    pub views: Vec<MsgView>,
+    pub body: Vec<u8>,
+}
+
+/// `sanitize_batch` with the decoded views (`nwc_sanitize_messages_view`): what the device decoded
+/// comes back, so Core builds its `Header` / `Vote` / `Certificate` from `(view, wire)` without
+/// bincode or base64.  Verdicts and votes are exactly `sanitize_batch`'s.  The
+/// call is not sharded: it runs whole on the calling thread's device, or on the signer's.
+/// Panics on a device failure.
+pub fn sanitize_batch_view(wires: &[&[u8]], states: &[FrameState], signer: Option<&Signer>)
+                           -> (Vec<(Verdict, Option<[u8; 64]>)>, BatchViews) {
+    assert_eq!(wires.len(), states.len());
+    init(0);
+    let m = wires.len();
+    if m == 0 {
+        return (Vec::new(), BatchViews { views: Vec::new(), body: Vec::new() });
+    }
+    let mut offsets = Vec::with_capacity(m + 1);
+    let mut data = Vec::new();
+    offsets.push(0u64);
+    for w in wires {
+        data.extend_from_slice(w);
+        offsets.push(data.len() as u64);
+    }
+    let total = data.len() as u64;
+    data.push(0);   // never an empty buffer
+    let gc_rounds: Vec<u64> = states.iter().map(|s| s.gc_round).collect();
+    let mut targets = vec![0u8; 80 * m];
+    for (i, s) in states.iter().enumerate() {
+        if let Some(t) = s.vote_target {
+            targets[80 * i..80 * i + 72].copy_from_slice(t);
+            targets[80 * i + 72] = 1;
+        }
+    }
+    let mut codes = vec![0i32; m];
+    let mut digests = vec![0u8; 32 * m];
+    let mut kinds = vec![3u8; m];
+    let mut sigs = vec![0u8; 64 * m];
+    let mut voted = vec![0u8; m];
+    let mut views: Vec<MsgView> = vec![unsafe { std::mem::zeroed() }; m];
+    let cap = unsafe { ffi::nwc_msg_view_body_bound(total, m as u64) } as usize;
+    let mut body = vec![0u8; cap];
+    let mut used = 0u64;
+    let rc = unsafe {
+        ffi::nwc_sanitize_messages_view(data.as_ptr(), offsets.as_ptr(), m, gc_rounds.as_ptr(), 0, targets.as_ptr(), std::ptr::null(),
+                                        signer.map_or(std::ptr::null_mut(), |s| s.h), codes.as_mut_ptr(), digests.as_mut_ptr(),
+                                        kinds.as_mut_ptr(), if signer.is_some() { sigs.as_mut_ptr() } else { std::ptr::null_mut() },
+                                        if signer.is_some() { voted.as_mut_ptr() } else { std::ptr::null_mut() },
+                                        views.as_mut_ptr() as *mut std::os::raw::c_void, body.as_mut_ptr(), cap, &mut used)
+    };
+    check(rc);
+    body.truncate(used as usize);
+    let verdicts = (0..m).map(|i| {
+        let mut v = Verdict { code: codes[i] as u32, digest: [0u8; 32], kind: kinds[i] };
+        v.digest.copy_from_slice(&digests[32 * i..32 * i + 32]);
+        let sig = if voted[i] != 0 {
+            let mut s = [0u8; 64];
+            s.copy_from_slice(&sigs[64 * i..64 * i + 64]);
+            Some(s)
+        } else {
+            None
+        };
+        (v, sig)
+    }).collect();
+    (verdicts, BatchViews { views, body })
+}
+
+/// One decoded message: its view, its wire bytes and the call's body.  The iterators read the wire
+/// only at the offsets the view names; entries come out in `BTreeMap` / `BTreeSet` order, so
+/// `BTreeMap::from_iter(entries.payload())` inserts already-sorted entries.
+pub struct ViewEntries<'a> {
+    pub view: &'a MsgView,
+    pub wire: &'a [u8],
+    pub body: &'a [u8],
+}
+
+impl<'a> ViewEntries<'a> {
+    /// `None` for a message that did not decode.
+    pub fn new(view: &'a MsgView, wire: &'a [u8], body: &'a [u8]) -> Option<Self> {
+        if view.decoded != 0 { Some(ViewEntries { view, wire, body }) } else { None }
+    }
+
+    fn area(&self, in_body: bool, off: u64, len: usize) -> &'a [u8] {
+        let src = if in_body { self.body } else { self.wire };
+        &src[off as usize..off as usize + len]
+    }
+
+    /// The header's or the vote's signature.
+    pub fn signature(&self) -> &'a [u8] {
+        &self.wire[self.view.sig_off as usize..self.view.sig_off as usize + 64]
+    }
+
+    /// `(digest, worker_id)` of `Header.payload`, ascending by digest.
+    pub fn payload(&self) -> impl Iterator<Item = (&'a [u8], u32)> + 'a {
+        let v = self.view;
+        let a = self.area(v.flags & ffi::NWC_VIEW_PAYLOAD_IN_BODY != 0, v.payload_off, 36 * v.n_payload as usize);
+        a.chunks_exact(36).map(|e| (&e[..32], u32::from_le_bytes([e[32], e[33], e[34], e[35]])))
+    }
+
+    /// `Header.parents`, ascending.
+    pub fn parents(&self) -> impl Iterator<Item = &'a [u8]> + 'a {
+        let v = self.view;
+        self.area(v.flags & ffi::NWC_VIEW_PARENTS_IN_BODY != 0, v.parents_off, 32 * v.n_parents as usize).chunks_exact(32)
+    }
+
+    /// `(member_index, signature)` of a certificate's votes in wire order; an index of -1 is a voter
+    /// outside the committee, whose key text lies at `vote_key_text`.
+    pub fn votes(&self) -> impl Iterator<Item = (i32, &'a [u8])> + 'a {
+        let wire = self.wire;
+        self.area(true, self.view.votes_off, 8 * self.view.n_votes as usize).chunks_exact(8).map(move |e| {
+            let idx = i32::from_le_bytes([e[0], e[1], e[2], e[3]]);
+            let off = u32::from_le_bytes([e[4], e[5], e[6], e[7]]) as usize;
+            let mut l = [0u8; 8];
+            l.copy_from_slice(&wire[off..off + 8]);
+            let sig = off + 8 + u64::from_le_bytes(l) as usize;
+            (idx, &wire[sig..sig + 64])
+        })
+    }
+
+    /// The base64 text of vote `k`'s key, for a voter whose index is -1.
+    pub fn vote_key_text(&self, k: usize) -> &'a [u8] {
+        let e = self.area(true, self.view.votes_off + 8 * k as u64, 8);
+        let off = u32::from_le_bytes([e[4], e[5], e[6], e[7]]) as usize;
+        let mut l = [0u8; 8];
+        l.copy_from_slice(&self.wire[off..off + 8]);
+        &self.wire[off + 8..off + 8 + u64::from_le_bytes(l) as usize]
+    }
+}
