@@ -335,6 +335,32 @@ int nwc_sanitizer_sanitize_vote(void* sanitizer, void* signer, const uint8_t* ms
                                 uint8_t vote_sig64[64], int32_t* voted);
 /* votes signed inside a group flight / by the one-message fallback.  Either pointer may be NULL. */
 int nwc_sanitizer_vote_stats(void* sanitizer, uint64_t* in_flight, uint64_t* alone);
+/* The device's decode from the same flight: nwc_sanitizer_sanitize_vote plus the
+ * message's nwc_msg_view record, which is declared below with the batch entries that return it.
+ *   view == NULL   the call IS nwc_sanitizer_sanitize_vote -- without a signer,
+ *                  nwc_sanitizer_sanitize -- and body, body_cap, body_used are ignored and untouched.
+ *   view != NULL   one nwc_msg_view record of 160 bytes.  body and body_used are required, body_cap >=
+ *                  nwc_msg_view_body_bound(len, 1); a call that breaks a rule returns NWC_ERR_ARG
+ *                  before anything is queued (nwc_sanitizer_stats does not move).  signer may be
+ *                  NULL: vote_sig64 and voted are then ignored; with a signer both are required and
+ *                  it must live on the sanitizer's device.
+ * The record, *body_used and the body areas the record names are what nwc_sanitize_messages_view
+ * returns for this message in a call of its own (m = 1, the same gc_round, vote_target and signer),
+ * the three body offsets included: one message's areas are handed out from offset 0 in the order
+ * payload, parents, voters.  A message that does not decode still gets its record (decoded = 0,
+ * kind, code).  On an error < 0 the record is zeroed and *body_used = 0.
+ *
+ * A group in which at least one request asks for a view gets one more launch (one wave per
+ * message) behind the result words and before the votes' launch; groups without such requests run
+ * exactly the launches they ran before.  A request whose message was redone or bypassed gets
+ * record and decision from one call of nwc_sanitize_messages_view. */
+int nwc_sanitizer_sanitize_view(void* sanitizer, void* signer /* or NULL */, const uint8_t* msg, size_t len,
+                                uint64_t gc_round, const uint8_t* vote_target, uint8_t digest32[32], uint8_t* kind,
+                                uint8_t vote_sig64[64], int32_t* voted, /* required with a signer, else ignored */
+                                void* view,                             /* one nwc_msg_view, or NULL */
+                                uint8_t* body, uint64_t body_cap, uint64_t* body_used);
+/* views delivered by a group flight / by the one-message fallback.  Either pointer may be NULL. */
+int nwc_sanitizer_view_stats(void* sanitizer, uint64_t* in_flight, uint64_t* alone);
 int nwc_sanitizer_destroy(void* sanitizer);
 
 /* Committee key cache (config/src/lib.rs:154-156 Committee).  Optional: verdicts never

@@ -73,6 +73,11 @@ _SIGS = {
                                                    _c_u8p, _c_u8p, _c_u8p, _c_u8p, ctypes.POINTER(ctypes.c_int32)]),
     "nwc_sanitizer_vote_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
                                                 ctypes.POINTER(ctypes.c_uint64)]),
+    "nwc_sanitizer_sanitize_view": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_u8p, ctypes.c_size_t, ctypes.c_uint64,
+                                                   _c_u8p, _c_u8p, _c_u8p, _c_u8p, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.c_void_p, _c_u8p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
+    "nwc_sanitizer_view_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint64),
+                                                ctypes.POINTER(ctypes.c_uint64)]),
     "nwc_sanitizer_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "nwc_set_committee": (ctypes.c_int, [_c_u8p, ctypes.c_size_t]),
     "nwc_cache_stats": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

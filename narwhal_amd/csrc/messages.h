@@ -766,20 +766,27 @@ __device__ __forceinline__ bool wire_ascending(const uint8_t* base, uint64_t src
   return __all(asc);
 }
 
-// One wave per message of the call, after k_finalize_messages (the codes are final; rec, rec_n, the
-// vote slots and the hashbuf slots are the parses').  Every exit is block-uniform: the records, the
-// codes and every wire field read here are the same in all lanes.  A message that did not decode --
-// or, which cannot happen, whose body areas would not fit -- gets decoded = 0 with its kind and code.
-__global__ __launch_bounds__(64) void k_message_views(MsgArgs a, Committee cm, const int32_t* __restrict__ codes, ViewOut o) {
-  const uint64_t i = blockIdx.x;
-  const u32 lane = threadIdx.x;
-  if (i >= a.m) return;   // block-uniform, as every exit below
+// The view of one message, shared by k_message_views (the batch entries) and k_view_group (the
+// sanitizer handle's flight): every lane of the wave calls it and gets the record's 40 words in w;
+// the return value is the body bytes the message took (0 when it has no body area or did not
+// decode).  rec, rec_n, the vote slots and the hashbuf slots are the parse's.  Every branch is
+// block-uniform: the records, the code and every wire field read here are the same in all lanes.  A
+// message that did not decode -- or, which cannot happen, whose body areas would not fit -- gets
+// decoded = 0 with its kind and code.  The policy `p` says where the message lies (beg, end: bytes of
+// a.data), what its code is, and how its body is placed:
+//   body()                   the base the record's body offsets count from;
+//   reserve(need, lane, at)  room for `need` bytes (a multiple of 16) at body() + at, false = none;
+//   canon<WORDS, MAP>(...)   canon_entries of a non-ascending sequence into its body area `dst`;
+//                            `slot` is where the parse put the same sequence in the hashbuf slot.
+template <class Pol>
+__device__ __forceinline__ uint64_t message_view(const MsgArgs& a, const Committee& cm, const uint64_t i, const u32 lane,
+                                                 const Pol& p, u32 w[VIEW_WORDS]) {
   const u32 r0 = a.rec[4 * i], kind = r0 & 255u;
-  const uint64_t beg = a.offsets[i], end = a.offsets[i + 1];
-  u32 w[VIEW_WORDS];
+  const uint64_t beg = p.beg(), end = p.end();
   _Pragma("unroll") for (int k = 0; k < VIEW_WORDS; ++k) w[k] = 0;
   bool ok = kind != MSG_OTHER && !(r0 & MF_PARSE_ERR) && ((end - beg) >> 32) == 0;
   u32 flags = 0;
+  uint64_t used = 0;
   if (ok && kind == MSG_VOTE) {
     MsgReader r{a.data, beg + 4, end, true, false};
     u32 id[8], origin[8], author[8];
@@ -832,37 +839,37 @@ __global__ __launch_bounds__(64) void k_message_views(MsgArgs a, Committee cm, c
     if (ok) {   // block-uniform
       const bool asc_p = wire_ascending<36>(r.base, pay_off, P, lane);
       const bool asc_q = wire_ascending<32>(r.base, par_off, Q, lane);
-      // three 16-byte-aligned areas from one bump of the allocator; a non-canonical sequence gets
-      // its wire count's room (canon_entries sorts in place)
+      // three 16-byte-aligned areas from one reservation; a non-canonical sequence gets its wire
+      // count's room (canon_entries sorts in place)
       const uint64_t need_p = asc_p ? 0 : (36 * P + 15) & ~(uint64_t)15;
       const uint64_t need_q = asc_q ? 0 : (32 * Q + 15) & ~(uint64_t)15;
       const uint64_t need_v = (8 * V + 15) & ~(uint64_t)15;
       const uint64_t need = need_p + need_q + need_v;
       uint64_t at = 0;
-      if (need) {
-        unsigned long long got = 0;
-        if (lane == 0) got = atomicAdd(o.body_used, (unsigned long long)need);
-        at = shfl_u64(got, 0);
-        ok = at <= o.body_cap && need <= o.body_cap - at;
-      }
+      if (need) ok = p.reserve(need, lane, at);
       if (ok) {   // block-uniform
+        used = need;
+        uint8_t* const body = p.body();
+        // the message's hashbuf slot: the digest input (10 words, the canonical payload, the
+        // canonical parents), then the voff[] entries past the wire counts' room
+        u32* const d = reinterpret_cast<u32*>(a.hashbuf + ((beg + 127) & ~(uint64_t)127) + 128 * i);
         uint64_t Pc = P, Qc = Q;
         uint64_t p_at = pay_off - beg, q_at = par_off - beg;
         if (!asc_p) {
           p_at = at;
-          Pc = canon_entries<9, true>(r.base, pay_off, P, reinterpret_cast<u32*>(o.body + p_at), lane);
+          Pc = p.template canon<9, true>(r.base, pay_off, P, reinterpret_cast<u32*>(body + p_at), d + 10, lane);
           flags |= VIEW_PAYLOAD_IN_BODY;
         }
         if (!asc_q) {
           q_at = at + need_p;
-          Qc = canon_entries<8, false>(r.base, par_off, Q, reinterpret_cast<u32*>(o.body + q_at), lane);
+          Qc = p.template canon<8, false>(r.base, par_off, Q, reinterpret_cast<u32*>(body + q_at), d + 10 + 9 * Pc, lane);
           flags |= VIEW_PARENTS_IN_BODY;
         }
         const uint64_t v_at = V ? at + need_p + need_q : 0;
         if (V) {
           const u32 vbase = a.rec[4 * i + 2];
-          const u32* voff = reinterpret_cast<const u32*>(a.hashbuf + ((beg + 127) & ~(uint64_t)127) + 128 * i) + 12 + 9 * P + 8 * Q;
-          uint2* out = reinterpret_cast<uint2*>(o.body + v_at);
+          const u32* voff = d + 12 + 9 * P + 8 * Q;
+          uint2* out = reinterpret_cast<uint2*>(body + v_at);
           const u32 rel = (u32)(votes_off - beg);
           for (uint64_t v = lane; v < V; v += 64) {
             u32 key[8];
@@ -893,7 +900,40 @@ __global__ __launch_bounds__(64) void k_message_views(MsgArgs a, Committee cm, c
     flags = 0;
   }
   w[0] = (ok ? 1u : 0u) | (kind << 8) | (flags << 16);
-  w[1] = (u32)codes[i];
+  w[1] = (u32)p.code();
+  return used;
+}
+
+// k_message_views' policy: the call's offsets and codes; the body's areas from one bump of the
+// call's allocator, the canonical form written where it stays.
+struct CallViewMsg {
+  const MsgArgs& a;
+  const uint64_t i;
+  const int32_t* codes;
+  const ViewOut& o;
+  __device__ __forceinline__ uint64_t beg() const { return a.offsets[i]; }
+  __device__ __forceinline__ uint64_t end() const { return a.offsets[i + 1]; }
+  __device__ __forceinline__ int32_t code() const { return codes[i]; }
+  __device__ __forceinline__ uint8_t* body() const { return o.body; }
+  __device__ __forceinline__ bool reserve(uint64_t need, u32 lane, uint64_t& at) const {
+    unsigned long long got = 0;
+    if (lane == 0) got = atomicAdd(o.body_used, (unsigned long long)need);
+    at = shfl_u64(got, 0);
+    return at <= o.body_cap && need <= o.body_cap - at;
+  }
+  template <int WORDS, bool MAP>
+  __device__ __forceinline__ uint64_t canon(const uint8_t* base, uint64_t src, uint64_t cnt, u32* dst, u32* /*slot*/, u32 lane) const {
+    return canon_entries<WORDS, MAP>(base, src, cnt, dst, lane);
+  }
+};
+
+// One wave per message of the call, after k_finalize_messages (the codes are final).
+__global__ __launch_bounds__(64) void k_message_views(MsgArgs a, Committee cm, const int32_t* __restrict__ codes, ViewOut o) {
+  const uint64_t i = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= a.m) return;   // block-uniform
+  u32 w[VIEW_WORDS];
+  (void)message_view(a, cm, i, lane, CallViewMsg{a, i, codes, o}, w);
   // lane k stores word k: one contiguous run of dwords per record
   u32 mine = 0;
   _Pragma("unroll") for (int k = 0; k < VIEW_WORDS; ++k) mine = lane == (u32)k ? w[k] : mine;
@@ -1071,6 +1111,75 @@ __global__ void k_finalize_group(const uint32_t* __restrict__ rec, const uint32_
   // system scope, release: the poller sees the digest and the kind once it sees the word
   __hip_atomic_store(out.results + i, GROUP_WRITTEN | (again ? GROUP_REDO : 0u) | ((neq < 0xFFFFu ? neq : 0xFFFFu) << 8) | (code & 255u),
                      __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ---- decoded views in the group flight (nwc_sanitizer_sanitize_view) -------------
+// The group's view requests, in the pinned group buffer: per message the "view wanted" byte, the
+// 160-byte record, the body bytes it used and the "written" flag byte; `body` is the group's body
+// area, in which message i owns [starts[i] + 64 i, starts[i] + lens[i] + 64 (i + 1)): starts are
+// 16-byte aligned and the ranges disjoint, so the regions are; each holds view_body_bound(len, 1).
+struct GroupViews {
+  const uint8_t* wanted;
+  uint32_t* views;     // VIEW_WORDS per message
+  uint32_t* used;
+  uint8_t* flags;      // bit 7 = the record, the body and `used` are in
+  uint8_t* body;
+};
+constexpr u32 GROUP_VIEW_SLACK = 64;
+
+// k_view_group's policy: the message's own range of the pinned data, the code of its result word,
+// the fixed body region (offsets count from its start).  The body is host memory other callers'
+// messages wait beside, and canon_entries sorts in place: so the canonical form is made where the
+// parse made it, in the message's hashbuf slot in HBM (the same call on the same bytes: it rewrites
+// what is there, and a payload that lost duplicates rewrites the parents behind it as the parse
+// did), and only the kept entries are copied out.  Nothing reads the slot's digest input after
+// k_verify_msg_group, and the voff[] entries lie past the wire counts' room, out of the sort's reach.
+struct GroupViewMsg {
+  const uint64_t b, len;
+  const u32 word;
+  uint8_t* const region;
+  __device__ __forceinline__ uint64_t beg() const { return b; }
+  __device__ __forceinline__ uint64_t end() const { return b + len; }
+  __device__ __forceinline__ int32_t code() const { return (int32_t)(word & 255u); }
+  __device__ __forceinline__ uint8_t* body() const { return region; }
+  __device__ __forceinline__ bool reserve(uint64_t need, u32, uint64_t& at) const {
+    at = 0;
+    return need <= len + GROUP_VIEW_SLACK;
+  }
+  template <int WORDS, bool MAP>
+  __device__ __forceinline__ uint64_t canon(const uint8_t* base, uint64_t src, uint64_t cnt, u32* dst, u32* slot, u32 lane) const {
+    const uint64_t kept = canon_entries<WORDS, MAP>(base, src, cnt, slot, lane);
+    for (uint64_t k = lane; k < WORDS * kept; k += 64) dst[k] = slot[k];
+    return kept;
+  }
+};
+
+// Behind k_finalize_group on the group's stream, only for a group in which some slot asks.  One
+// wave per message.  Block i leaves at once (block-uniformly) unless slot i asks, its result word
+// is written and does not say "decide me again".  a is the group parse's MsgArgs.
+__global__ __launch_bounds__(64) void k_view_group(MsgArgs a, Committee cm, GroupViews g, const uint32_t* results,
+                                                   const uint64_t* __restrict__ starts, const uint32_t* __restrict__ lens,
+                                                   uint32_t nmsg) {
+  const uint32_t i = blockIdx.x;
+  const u32 lane = threadIdx.x;
+  if (i >= nmsg) return;   // block-uniform, as every exit below
+  // the wanted byte, then the word: the host clears a slot's word before it writes a non-zero byte
+  // there, so a block of an earlier group's launch that is still running never pairs a new request
+  // with an old word
+  if (!__hip_atomic_load(g.wanted + i, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM)) return;
+  const u32 word = __hip_atomic_load(results + i, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (!(word & GROUP_WRITTEN) || (word & GROUP_REDO)) return;
+  const uint64_t beg = starts[i], len = lens[i];
+  u32 w[VIEW_WORDS];
+  const uint64_t used = message_view(a, cm, i, lane, GroupViewMsg{beg, len, word, g.body + beg + (uint64_t)GROUP_VIEW_SLACK * i}, w);
+  // lane k stores word k; then `used`; then, once every lane's stores are out, the flag
+  u32 mine = 0;
+  _Pragma("unroll") for (int k = 0; k < VIEW_WORDS; ++k) mine = lane == (u32)k ? w[k] : mine;
+  if (lane < (u32)VIEW_WORDS) __hip_atomic_store(g.views + VIEW_WORDS * (size_t)i + lane, mine, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  if (lane == 0) __hip_atomic_store(g.used + i, (u32)used, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  __threadfence_system();
+  __syncthreads();
+  if (lane == 0) __hip_atomic_store(g.flags + i, (uint8_t)0x80u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // code[i] in the reference's order:

@@ -92,7 +92,8 @@ constexpr size_t MSG_VIEW_BYTES = 160;
 // What the body of a view call can hold at most: per message 36 P + 32 Q + 8 V bytes in three
 // 16-byte-aligned areas (<= 45 bytes of alignment), less than its wire length + 64 (a header's fixed
 // fields alone take more than 160 bytes, a payload entry 36, a parent 32 and a vote >= 72).
-inline uint64_t view_body_bound(uint64_t total, uint64_t m) { return total + 64 * m; }
+constexpr uint64_t SAN_VIEW_SLACK = 64;   // per message, on top of its wire length
+inline uint64_t view_body_bound(uint64_t total, uint64_t m) { return total + SAN_VIEW_SLACK * m; }
 inline CallArena call_arena(size_t m, uint64_t total, bool own_state = false, bool votes = false, bool views = false) {
   ArenaWalk w;
   CallArena a{};
@@ -170,12 +171,16 @@ inline MsgArena msg_arena(size_t m, uint64_t total, uint64_t vt, bool ysplit, bo
 //     per-message starts, lengths, gc_rounds and vote targets (80 B), and on the way back the result
 //     words, digests and kinds; then what a vote request adds (nwc_sanitizer_sanitize_vote): the
 //     device address of the signer's key record (8 B, 0 = no vote asked), the vote's signature
-//     (64 B) and its "written" byte.
+//     (64 B) and its "written" byte; then what a view request adds (nwc_sanitizer_sanitize_view):
+//     the "view wanted" byte, the 160-byte record, the body bytes it used (u32) and the view's
+//     "written" byte per message, and the group's body area of byte_cap + 64 max_msgs bytes, of
+//     which message i owns [starts[i] + 64 i, starts[i] + lens[i] + 64 (i + 1)).
 //   SanScratch: the HBM scratch of the handle (one group runs at a time on the device's stream).
 //     eq_msg is followed by cdig (one digest array of 2 x max_msgs); `counters` is the vote-slot
 //     allocator and the list count.
 struct SanGroupBuf {
   size_t data, starts, lens, gc_rounds, targets, results, digests, kinds, vote_keys, vote_sigs, vote_flags;
+  size_t view_wanted, views, view_used, view_flags, view_body;
   size_t bytes;
 };
 inline SanGroupBuf san_group_buf(size_t max_msgs, uint64_t byte_cap) {
@@ -192,6 +197,11 @@ inline SanGroupBuf san_group_buf(size_t max_msgs, uint64_t byte_cap) {
   a.vote_keys = w.take(8 * max_msgs);
   a.vote_sigs = w.take(64 * max_msgs);
   a.vote_flags = w.take(max_msgs);
+  a.view_wanted = w.take(max_msgs);
+  a.views = w.take(MSG_VIEW_BYTES * max_msgs);
+  a.view_used = w.take(4 * max_msgs);
+  a.view_flags = w.take(max_msgs);
+  a.view_body = w.take(byte_cap + SAN_VIEW_SLACK * max_msgs);
   a.bytes = w.off;
   return a;
 }

@@ -25,6 +25,17 @@
 // says Ok + header.  Such a member polls its flag byte after its result word.  A vote the flight did
 // not deliver (flag unwritten, message redone or bypassed) comes from Backend::vote_alone, asked
 // only once the message's code is known to be Ok and its kind a header: never speculatively.
+//
+// A request may also ask for the device's decode of its message (submit's view: a 160-byte
+// nwc_msg_view record plus a body).  The protocol is the vote's: every member writes its slot's
+// "view wanted" byte, 0 included, and clears its view flag byte; the backend's launch builds the
+// records of the slots that ask, each body in the slot's own region of the group's body area
+// (view_region: no allocator, nothing to reset between groups).  Such a member polls its view flag
+// after its result word and before its vote flag -- the backend queues the views before the votes,
+// so a member that wants only the cheap one does not wait for a signature, and polling in stream
+// order costs a member that wants both nothing: when the later flag is in the earlier one is.  A
+// view the flight did not deliver comes from Backend::view_alone, which for a message that was
+// redone or bypassed also DECIDES it (redo / bypass are then not called: one decision, not two).
 #pragma once
 
 #include <atomic>
@@ -63,9 +74,29 @@ struct GroupBuf {
   uint64_t* vote_keys = nullptr;  // per message: the vote request's key (0 = none); null: a backend without votes
   uint8_t* vote_sigs = nullptr;   // per message, 64 B: written before the vote flag
   uint8_t* vote_flags = nullptr;  // per message: bit 7 = the vote's signature is in
+  uint8_t* view_wanted = nullptr; // per message: non-zero = a view is asked for; null: a backend without views
+  uint8_t* views = nullptr;       // per message, VIEW_BYTES: written before the view flag
+  uint32_t* view_used = nullptr;  // per message: the body bytes the view took, written before the view flag
+  uint8_t* view_flags = nullptr;  // per message: bit 7 = the record, its body and view_used are in
+  uint8_t* view_body = nullptr;   // the group's body area: byte_cap + VIEW_SLACK * max_messages bytes
 };
 
 constexpr uint8_t VOTE_WRITTEN = 0x80;
+constexpr uint8_t VIEW_WRITTEN = 0x80;
+constexpr size_t VIEW_BYTES = 160;    // one nwc_msg_view
+constexpr uint64_t VIEW_SLACK = 64;   // a message's body holds at most its length + VIEW_SLACK bytes
+inline uint64_t view_body_bound(uint64_t len) { return len + VIEW_SLACK; }   // nwc_msg_view_body_bound(len, 1)
+// where slot `slot` of a group, whose bytes start at `start` of the data, has its body region
+inline uint64_t view_region(uint64_t start, uint32_t slot) { return start + VIEW_SLACK * slot; }
+
+// A request's view outputs: the record (VIEW_BYTES), the body (cap >= view_body_bound(len)) and the
+// body bytes in use.  All three are required.
+struct ViewReq {
+  uint8_t* rec = nullptr;
+  uint8_t* body = nullptr;
+  uint64_t body_cap = 0;
+  uint64_t* body_used = nullptr;
+};
 constexpr uint32_t KIND_HEADER = 0;   // PrimaryMessage::Header, as the kinds array and the kind output carry it
 
 struct Backend {
@@ -89,12 +120,20 @@ struct Backend {
                          uint8_t* /*sig64*/) {
     return NWC_ERR_ARG;
   }
+  // Decide one message outside a group AND hand back its view: the code >= 0 with digest32, kind,
+  // the record and the body filled (*body_used bytes of it), or an error < 0.  A backend without
+  // views keeps this default.
+  virtual int view_alone(const uint8_t* /*msg*/, size_t /*len*/, uint64_t /*gc_round*/, const uint8_t* /*vote_target*/,
+                         uint8_t* /*digest32*/, uint8_t* /*kind*/, const ViewReq& /*out*/) {
+    return NWC_ERR_ARG;
+  }
 };
 
 struct Stats {
   uint64_t groups = 0, messages = 0, bytes = 0, equations = 0, redone_messages = 0, bypassed_messages = 0,
            max_messages_in_group = 0, reserved = 0;
   uint64_t votes_in_flight = 0, votes_alone = 0;   // votes signed inside a group flight / by vote_alone
+  uint64_t views_in_flight = 0, views_alone = 0;   // views built inside a group flight / by view_alone
 };
 
 class Queue {
@@ -119,10 +158,22 @@ class Queue {
   // vote_key != 0 asks for Vote::new under that key when the message is a header and its code is
   // Ok: vote_sig (64 bytes) then holds the signature and *voted is 1; otherwise -- an error
   // included -- *voted is 0 and vote_sig is zeroed.  Both are required with a key.
+  // view != nullptr asks for the message's view: its three outputs are required and body_cap >=
+  // view_body_bound(len), else NWC_ERR_ARG before anything is queued.  On an error < 0 the record is
+  // zeroed and *body_used is 0.
   int submit(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32, uint8_t* kind,
-             bool direct = false, uint64_t vote_key = 0, uint8_t* vote_sig = nullptr, int* voted = nullptr) {
+             bool direct = false, uint64_t vote_key = 0, uint8_t* vote_sig = nullptr, int* voted = nullptr,
+             const ViewReq* view = nullptr) {
     if (vote_sig) std::memset(vote_sig, 0, 64);
     if (voted) *voted = 0;
+    View vw;
+    if (view) {
+      vw.out = *view;
+      vw.asked = true;
+      if (vw.out.rec) std::memset(vw.out.rec, 0, VIEW_BYTES);
+      if (vw.out.body_used) *vw.out.body_used = 0;
+      if (!vw.out.rec || !vw.out.body || !vw.out.body_used || vw.out.body_cap < view_body_bound(len)) return NWC_ERR_ARG;
+    }
     if (vote_key && (!vote_sig || !voted)) return NWC_ERR_ARG;
     std::unique_lock<std::mutex> lk(mu_);
     if (stopping_) return NWC_ERR_NOT_INIT;
@@ -134,17 +185,24 @@ class Queue {
       lk.unlock();
       // (the vote needs the digest and the kind whether or not the caller asked for them)
       uint8_t dig[32], kd = 0xFF;
-      rc = be_.bypass(msg, len, gc_round, vote_target, vote_key ? dig : digest32, vote_key ? &kd : kind);
+      rc = outside(false, msg, len, gc_round, vote_target, vote_key ? dig : digest32, vote_key ? &kd : kind, vw);
       if (vote_key && rc >= 0 && (rc = vote_outside(msg, len, rc, dig, kd, v)) >= 0) {   // (an error touches no output)
         if (digest32) std::memcpy(digest32, dig, 32);
         if (kind) *kind = kd;
       }
       lk.lock();
     } else {
-      rc = grouped(lk, msg, len, gc_round, vote_target, digest32, kind, v);
+      rc = grouped(lk, msg, len, gc_round, vote_target, digest32, kind, v, vw);
+    }
+    if (rc < 0 && vw.asked) {
+      std::memset(vw.out.rec, 0, VIEW_BYTES);
+      *vw.out.body_used = 0;
+      vw.in_flight = vw.alone = false;
     }
     stats_.votes_in_flight += v.in_flight ? 1 : 0;
     stats_.votes_alone += v.alone ? 1 : 0;
+    stats_.views_in_flight += vw.in_flight ? 1 : 0;
+    stats_.views_alone += vw.alone ? 1 : 0;
     if (--users_ == 0) signal();
     return rc;
   }
@@ -172,6 +230,23 @@ class Queue {
     int* voted;
     bool in_flight = false, alone = false;
   };
+  // one request's view: where it goes and which route delivered it
+  struct View {
+    ViewReq out;
+    bool asked = false, in_flight = false, alone = false;
+  };
+  // a message decided outside a group: by redo / bypass, or -- a view request -- by view_alone, which
+  // decides it and builds its view in one call.  Returns the code, or the backend's error.
+  int outside(bool again, const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32,
+              uint8_t* kind, View& vw) {
+    if (!vw.asked)
+      return again ? be_.redo(msg, len, gc_round, vote_target, digest32, kind)
+                   : be_.bypass(msg, len, gc_round, vote_target, digest32, kind);
+    const int rc = be_.view_alone(msg, len, gc_round, vote_target, digest32, kind, vw.out);
+    if (rc >= 0 && *vw.out.body_used > vw.out.body_cap) return NWC_ERR_DEVICE;
+    vw.alone = rc >= 0;
+    return rc;
+  }
   // a message decided outside a group (redo, bypass) or whose flag stayed unwritten: the vote comes
   // from the backend, and only for an Ok header.  Returns the code, or vote_alone's error.
   int vote_outside(const uint8_t* msg, size_t len, int code, const uint8_t* id32, uint8_t kind, Vote& v) {
@@ -242,7 +317,7 @@ class Queue {
   }
 
   int grouped(std::unique_lock<std::mutex>& lk, const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target,
-              uint8_t* digest32, uint8_t* kind, Vote& v) {
+              uint8_t* digest32, uint8_t* kind, Vote& v, View& vw) {
     // a place in the open group, or a free buffer to open the next one in
     int b = -1;
     bool leader = false;
@@ -296,6 +371,13 @@ class Queue {
       if (v.key) __atomic_thread_fence(__ATOMIC_SEQ_CST);
       __atomic_store_n(gb.vote_keys + slot, v.key, __ATOMIC_RELEASE);   // 0 included: the previous group's key goes
     }
+    if (gb.view_wanted) {
+      // the same order for the view: flag and word cleared, a full fence, then a non-zero wanted
+      // byte -- the view launch reads the byte first and the word second
+      __atomic_store_n(gb.view_flags + slot, (uint8_t)0, __ATOMIC_RELAXED);
+      if (vw.asked) __atomic_thread_fence(__ATOMIC_SEQ_CST);
+      __atomic_store_n(gb.view_wanted + slot, (uint8_t)(vw.asked ? 1 : 0), __ATOMIC_RELEASE);   // 0 included
+    }
     lk.lock();
     if (--g.copying == 0) signal();
 
@@ -334,7 +416,7 @@ class Queue {
     if (rc == 0) {
       const clock::time_point t0 = g.t_launch;
       lk.unlock();
-      rc = collect(b, gb, slot, msg, len, gc_round, vote_target, t0, digest32, kind, redone, equations, v);
+      rc = collect(b, gb, slot, msg, len, gc_round, vote_target, t0, digest32, kind, redone, equations, v, vw);
       lk.lock();
     }
     stats_.redone_messages += redone ? 1 : 0;
@@ -355,7 +437,7 @@ class Queue {
   // a member's own result: poll its word, fall back to the backend's wait, redo if it asks for it
   int collect(int b, const GroupBuf& gb, uint32_t slot, const uint8_t* msg, size_t len, uint64_t gc_round,
               const uint8_t* vote_target, clock::time_point t0, uint8_t* digest32, uint8_t* kind, bool& redone,
-              uint32_t& equations, Vote& v) {
+              uint32_t& equations, Vote& v, View& vw) {
     uint32_t w = 0;
     for (uint32_t spins = 0; !((w = __atomic_load_n(gb.results + slot, __ATOMIC_ACQUIRE)) & R_WRITTEN); ++spins) {
       if ((spins & 255) == 255 && clock::now() - t0 > poll_timeout_) {
@@ -367,9 +449,9 @@ class Queue {
     }
     if (!(w & R_WRITTEN) || (w & R_REDO)) {   // unwritten after the wait, or "decide me again"
       redone = true;
-      if (!v.key) return be_.redo(msg, len, gc_round, vote_target, digest32, kind);
+      if (!v.key) return outside(true, msg, len, gc_round, vote_target, digest32, kind, vw);
       uint8_t dig[32], kd = 0xFF;
-      int rc = be_.redo(msg, len, gc_round, vote_target, dig, &kd);
+      int rc = outside(true, msg, len, gc_round, vote_target, dig, &kd, vw);
       if (rc < 0 || (rc = vote_outside(msg, len, rc, dig, kd, v)) < 0) return rc;
       if (digest32) std::memcpy(digest32, dig, 32);
       if (kind) *kind = kd;
@@ -378,6 +460,37 @@ class Queue {
     equations = result_equations(w);
     const int code = (int)result_code(w);
     const uint8_t kd = gb.kinds[slot];
+    if (vw.asked) {
+      // the flight builds the views behind the result words and before the votes: poll the slot's
+      // view flag first, under the same time limit
+      bool in = false;
+      if (gb.view_flags) {
+        auto written = [&] { return (__atomic_load_n(gb.view_flags + slot, __ATOMIC_ACQUIRE) & VIEW_WRITTEN) != 0; };
+        for (uint32_t spins = 0; !(in = written()); ++spins) {
+          if ((spins & 255) == 255 && clock::now() - t0 > poll_timeout_) {
+            if (int rc = be_.wait(b)) return rc;
+            in = written();
+            break;
+          }
+          relax(spins);
+        }
+      }
+      if (in) {
+        const uint32_t used = gb.view_used[slot];
+        if (used > view_body_bound(len)) return NWC_ERR_DEVICE;   // (cap >= the bound was checked on entry)
+        std::memcpy(vw.out.rec, gb.views + VIEW_BYTES * (size_t)slot, VIEW_BYTES);
+        if (used) std::memcpy(vw.out.body, gb.view_body + view_region(gb.starts[slot], slot), used);
+        *vw.out.body_used = used;
+        vw.in_flight = true;
+      } else {
+        // the flight's code, digest and kind stand; the batch entry's record must agree with them
+        uint8_t dig[32], k2 = 0xFF;
+        const int rc = be_.view_alone(msg, len, gc_round, vote_target, dig, &k2, vw.out);
+        if (rc < 0) return rc;
+        if (rc != code || k2 != kd || *vw.out.body_used > vw.out.body_cap) return NWC_ERR_DEVICE;
+        vw.alone = true;
+      }
+    }
     if (v.key && code == 0 && kd == KIND_HEADER) {
       // the flight signs after the result words: poll the slot's flag under the same time limit
       bool in = false;

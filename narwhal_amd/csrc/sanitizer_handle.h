@@ -21,7 +21,22 @@
 // deliver (the message was redone or bypassed, or the flag stayed unwritten) is signed by
 // vote_alone: the header's author string and round cross the device's pinned stage and k_vote_wire
 // decodes them as the parse does -- the host has no base64 decoder.
+//
+// Decoded views in the flight (nwc_sanitizer_sanitize_view): a request may ask for its
+// message's nwc_msg_view.  A group with at least one such slot gets k_view_group behind
+// k_finalize_group and before k_vote_group: one wave per message, which builds the record and the
+// body of the slots that ask, from what the group's parse left in the scratch, into the slot's own
+// region of the pinned buffer.  A view the flight did not deliver (the message was redone or
+// bypassed, or the flag stayed unwritten) comes from view_alone: nwc_sanitize_messages_view on the
+// one message, which for a redone or bypassed message is also its decision.
 #include "sanitize_queue.h"
+
+// one slack, spelled where each layer needs it: the kernel's region arithmetic, the queue's, the
+// pinned layout's body area (byte_cap + slack x messages) and the bound the callers size a body by
+static_assert(nwc::GROUP_VIEW_SLACK == nwc::sq::VIEW_SLACK && nwc::plan::SAN_VIEW_SLACK == nwc::sq::VIEW_SLACK,
+              "the view body slack differs between messages.h, sanitize_queue.h and msg_plan.h");
+static_assert(nwc::sq::VIEW_BYTES == nwc::plan::MSG_VIEW_BYTES && nwc::sq::VIEW_BYTES == 4 * nwc::VIEW_WORDS,
+              "the view record's size differs between the layers");
 
 namespace {
 
@@ -51,6 +66,11 @@ struct Sanitizer final : nwc::sq::Backend {
     g.vote_keys = reinterpret_cast<uint64_t*>(p + gl.vote_keys);
     g.vote_sigs = p + gl.vote_sigs;
     g.vote_flags = p + gl.vote_flags;
+    g.view_wanted = p + gl.view_wanted;
+    g.views = p + gl.views;
+    g.view_used = reinterpret_cast<uint32_t*>(p + gl.view_used);
+    g.view_flags = p + gl.view_flags;
+    g.view_body = p + gl.view_body;
     return g;
   }
   nwc::sq::GroupBuf buffer(int b) override { return view(host[b]->get()); }
@@ -73,6 +93,13 @@ struct Sanitizer final : nwc::sq::Backend {
         __atomic_store_n(h.results + i, nwc::sq::R_WRITTEN | nwc::sq::R_REDO, __ATOMIC_RELEASE);
       return 0;
     }
+    // what the members ask for, and everything that can fail without a launch, before anything is
+    // queued: a group that fails frees its buffer at once, so no launch of it may be left behind
+    bool views = false, votes = false;
+    for (uint32_t i = 0; i < nmsg && !views; ++i) views = h.view_wanted[i] != 0;
+    for (uint32_t i = 0; i < nmsg && !votes; ++i) votes = h.vote_keys[i] != 0;
+    if (votes)
+      if (int rc = ensure_sign_table(dc)) return rc;
     uint8_t* const base = scratch->get();
     uint32_t* const counters = arena_at<uint32_t>(base, sl.counters);
     const hipStream_t s = dc.stream;
@@ -128,16 +155,26 @@ struct Sanitizer final : nwc::sq::Backend {
                        knobs().sanitizer_redo_every.load(), counters, counters + 1);
     HIP_TRY(hipGetLastError());
     counters_dirty = false;
+    // the views of the slots that ask, once their result words are out (stream order) and before the
+    // votes: a view is a few loads and stores, a vote a signature
+    if (views) {
+      hipLaunchKernelGGL(nwc::k_view_group, dim3(nmsg), dim3(64), 0, s, a, cm,
+                         nwc::GroupViews{g.view_wanted, reinterpret_cast<uint32_t*>(g.views), g.view_used, g.view_flags, g.view_body},
+                         (const uint32_t*)g.results, (const uint64_t*)g.starts, (const uint32_t*)g.lens, nmsg);
+      HIP_TRY(hipGetLastError());
+    }
     // Vote::new for the slots that carry a key, once their result words are out (stream order)
-    bool votes = false;
-    for (uint32_t i = 0; i < nmsg && !votes; ++i) votes = h.vote_keys[i] != 0;
     if (votes) {
-      if (int rc = ensure_sign_table(dc)) return rc;
       hipLaunchKernelGGL(nwc::k_vote_group, dim3(nmsg), dim3(64), 0, s, (const nwc::ge_niels*)dc.sign_table,
                          nwc::GroupVotes{g.vote_keys, g.vote_sigs, g.vote_flags}, (const uint32_t*)g.results,
                          (const uint32_t*)a.rec, (const uint8_t*)a.digests, (const uint8_t*)a.eq_pk, a.data,
                          (const uint64_t*)g.starts, (const uint32_t*)g.lens, nmsg);
-      HIP_TRY(hipGetLastError());
+      if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
+        // the view launch is queued and writes into this buffer: it must have ended before the
+        // group's members, who all leave with this error, give the buffer to the next group
+        if (views) (void)hipStreamSynchronize(s);
+        return set_err(NWC_ERR_DEVICE, "k_vote_group launch failed: %s", hipGetErrorString(e));
+      }
     }
     return 0;
   }
@@ -164,6 +201,18 @@ struct Sanitizer final : nwc::sq::Backend {
   int bypass(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32,
              uint8_t* kind) override {
     return alone(msg, len, gc_round, vote_target, digest32, kind);
+  }
+
+  // the batch entry's view call on this one message: its decision and its view
+  int view_alone(const uint8_t* msg, size_t len, uint64_t gc_round, const uint8_t* vote_target, uint8_t* digest32, uint8_t* kind,
+                 const nwc::sq::ViewReq& out) override {
+    static const uint8_t none[16] = {0};
+    const uint64_t offs[2] = {0, (uint64_t)len};
+    int32_t code = 0;
+    const int rc = nwc_sanitize_messages_view(len ? msg : none, offs, 1, nullptr, gc_round, nullptr, vote_target, nullptr, &code,
+                                              digest32, kind, nullptr, nullptr, out.rec, out.body, (size_t)out.body_cap,
+                                              out.body_used);
+    return rc < 0 ? rc : (int)code;
   }
 
   // Vote::new for one header the batch entry has accepted.  Only the bytes the vote needs cross
@@ -326,6 +375,52 @@ int nwc_sanitizer_sanitize_vote(void* sanitizer, void* signer, const uint8_t* ms
   if (rc == NWC_ERR_NOT_INIT && t_code != NWC_ERR_NOT_INIT)
     return set_err(rc, "the sanitizer was destroyed or its device context shut down");
   return rc;
+}
+
+int nwc_sanitizer_sanitize_view(void* sanitizer, void* signer, const uint8_t* msg, size_t len, uint64_t gc_round,
+                                const uint8_t* vote_target, uint8_t digest32[32], uint8_t* kind, uint8_t vote_sig64[64],
+                                int32_t* voted, void* view, uint8_t* body, uint64_t body_cap, uint64_t* body_used) {
+  if (!view)
+    return signer ? nwc_sanitizer_sanitize_vote(sanitizer, signer, msg, len, gc_round, vote_target, digest32, kind, vote_sig64, voted)
+                  : nwc_sanitizer_sanitize(sanitizer, msg, len, gc_round, vote_target, digest32, kind);
+  // on an error < 0 the record is zero and no body byte is in use
+  std::memset(view, 0, nwc::sq::VIEW_BYTES);
+  if (body_used) *body_used = 0;
+  if (signer && vote_sig64) std::memset(vote_sig64, 0, 64);
+  if (signer && voted) *voted = 0;
+  if (!sanitizer) return set_err(NWC_ERR_ARG, "null sanitizer");
+  if (signer && (!vote_sig64 || !voted)) return set_err(NWC_ERR_ARG, "null vote output");
+  if (len && !msg) return set_err(NWC_ERR_ARG, "null message");
+  if (!body || !body_used) return set_err(NWC_ERR_ARG, "a view needs body and body_used");
+  if (len >> 32) return set_err(NWC_ERR_ARG, "the message is 2^32 bytes or longer");
+  if (body_cap < nwc::plan::view_body_bound(len, 1)) return set_err(NWC_ERR_ARG, "body_cap is below nwc_msg_view_body_bound(len, 1)");
+  if (int rc = require_init()) return rc;
+  Sanitizer& v = *static_cast<Sanitizer*>(sanitizer);
+  uint64_t key = 0;
+  if (signer) {
+    Signer& sg = *static_cast<Signer*>(signer);
+    if (!sg.d || !sg.key) return set_err(NWC_ERR_NOT_INIT, "the signer's device context was shut down");
+    DevCtx* const vd = v.d.load();
+    if (!vd) return set_err(NWC_ERR_NOT_INIT, "the sanitizer was destroyed or its device context shut down");
+    if (vd != sg.d) return set_err(NWC_ERR_ARG, "the signer lives on another device than the sanitizer");
+    key = (uint64_t)reinterpret_cast<uintptr_t>(sg.key);
+  }
+  const nwc::sq::ViewReq vr{static_cast<uint8_t*>(view), body, body_cap, body_used};
+  t_code = 0;
+  const int rc = v.q->submit(msg, len, gc_round, vote_target, digest32, kind, !Sanitizer::groupable(), key,
+                             signer ? vote_sig64 : nullptr, signer ? voted : nullptr, &vr);
+  if (rc == NWC_ERR_NOT_INIT && t_code != NWC_ERR_NOT_INIT)
+    return set_err(rc, "the sanitizer was destroyed or its device context shut down");
+  return rc;
+}
+
+int nwc_sanitizer_view_stats(void* sanitizer, uint64_t* in_flight, uint64_t* alone) {
+  if (!sanitizer) return set_err(NWC_ERR_ARG, "null sanitizer");
+  if (int rc = require_init()) return rc;
+  const nwc::sq::Stats s = static_cast<Sanitizer*>(sanitizer)->q->stats();
+  if (in_flight) *in_flight = s.views_in_flight;
+  if (alone) *alone = s.views_alone;
+  return 0;
 }
 
 int nwc_sanitizer_vote_stats(void* sanitizer, uint64_t* in_flight, uint64_t* alone) {

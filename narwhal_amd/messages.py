@@ -202,13 +202,15 @@ class Sanitizer:
     and `target` belong to the call.  A group closes at `max_messages` messages (0 = as many as
     fit), when it is full, or `max_wait_us` after it was opened (0 = never wait for company).  The
     committee is the one last installed (`Committee.install`).  A context manager; `close()` lets
-    queued requests finish.  `lib`: a loaded library (tests)."""
+    queued requests finish.  `lib`: a loaded library (tests).  `committee`: the installed committee,
+    which `sanitize_view` needs to name a certificate's voters (views carry committee indices)."""
 
     STATS = ("groups", "messages", "bytes", "equations", "redone_messages", "bypassed_messages",
              "max_messages_in_group", "reserved")
 
-    def __init__(self, max_messages: int = 0, max_wait_us: int = 0, lib=None):
+    def __init__(self, max_messages: int = 0, max_wait_us: int = 0, lib=None, committee: Optional[Committee] = None):
         self._lib = lib if lib is not None else _lib.load()
+        self.committee = committee
         self.handle = self._lib.nwc_sanitizer_create(max_messages, max_wait_us)
         if not self.handle:
             raise _lib.DeviceError("nwc_sanitizer_create failed (%d): %s" % (self._lib.nwc_last_error_code(),
@@ -249,6 +251,42 @@ class Sanitizer:
         """Votes signed inside a group flight / by the one-message fallback."""
         a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
         _lib.check(self._lib.nwc_sanitizer_vote_stats(self.handle, ctypes.byref(a), ctypes.byref(b)))
+        return {"in_flight": int(a.value), "alone": int(b.value)}
+
+    def sanitize_view(self, wire: bytes, gc_round: int = 0, target: Optional[Header] = None,
+                      signer: Optional[Signer] = None) -> tuple:
+        """`sanitize_vote`'s tuple (the signature None without a signer) plus the Header / Vote /
+        Certificate the device decoded in the same flight (nwc_sanitizer_sanitize_view), built by
+        `_view_objects` from the record, the wire and the body; None for a message that did not
+        decode.  A certificate's voters are named through `committee` (the constructor's)."""
+        wire = bytes(wire)
+        t = _target72(target)
+        dig = ctypes.create_string_buffer(32)
+        kind = ctypes.create_string_buffer(1)
+        sig = ctypes.create_string_buffer(64) if signer is not None else None
+        voted = ctypes.c_int32(0)
+        view = _lib.MsgView()
+        cap = int(self._lib.nwc_msg_view_body_bound(len(wire), 1))
+        body = ctypes.create_string_buffer(cap)
+        used = ctypes.c_uint64(0)
+        code = self._lib.nwc_sanitizer_sanitize_view(self.handle, signer.handle if signer is not None else None,
+                                                     _lib.buf(wire) if wire else None, len(wire), gc_round,
+                                                     _lib.buf(t) if t else None, dig, kind, sig,
+                                                     ctypes.byref(voted) if signer is not None else None,
+                                                     ctypes.byref(view), body, cap, ctypes.byref(used))
+        obj = None
+        if code >= 0 and view.decoded:
+            if view.n_votes and self.committee is None:
+                raise ValueError("Sanitizer(committee=...) is needed to name a certificate's voters")
+            keys = list(self.committee.authorities) if self.committee is not None else []
+            obj = _view_objects(view, wire, body.raw[:used.value], keys)
+        return (int(code), Digest(dig.raw), kind.raw[0],
+                Signature.from_bytes(sig.raw) if signer is not None and voted.value else None, obj)
+
+    def view_stats(self) -> dict:
+        """Views delivered by a group flight / by the one-message fallback."""
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(self._lib.nwc_sanitizer_view_stats(self.handle, ctypes.byref(a), ctypes.byref(b)))
         return {"in_flight": int(a.value), "alone": int(b.value)}
 
     def check(self, wire: bytes, gc_round: int = 0, target: Optional[Header] = None) -> Tuple[Digest, int]:

@@ -101,6 +101,11 @@ extern "C" {
                                        vote_target: *const u8, digest32: *mut u8, kind: *mut u8, vote_sig64: *mut u8,
                                        voted: *mut i32) -> c_int;
     pub fn nwc_sanitizer_vote_stats(sanitizer: *mut c_void, in_flight: *mut u64, alone: *mut u64) -> c_int;
+    pub fn nwc_sanitizer_sanitize_view(sanitizer: *mut c_void, signer: *mut c_void, msg: *const u8, len: usize, gc_round: u64,
+                                       vote_target: *const u8, digest32: *mut u8, kind: *mut u8, vote_sig64: *mut u8,
+                                       voted: *mut i32, view: *mut c_void, body: *mut u8, body_cap: u64,
+                                       body_used: *mut u64) -> c_int;
+    pub fn nwc_sanitizer_view_stats(sanitizer: *mut c_void, in_flight: *mut u64, alone: *mut u64) -> c_int;
     pub fn nwc_sanitizer_destroy(sanitizer: *mut c_void) -> c_int;
     pub fn nwc_set_committee(pks: *const u8, n: usize) -> c_int;
     pub fn nwc_cache_stats(committee_keys: *mut u32, auto_keys: *mut u32) -> c_int;

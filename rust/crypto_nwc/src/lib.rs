@@ -411,6 +411,37 @@ impl Sanitizer {
         (v, if voted != 0 { Some(sig) } else { None })
     }
 
+    /// `sanitize_vote` (`signer`: `None` = `sanitize`) plus what the device decoded, from the same
+    /// flight: the message's `MsgView` and the body its offsets point into (`ViewEntries::new(&view,
+    /// wire, &body)`), so that Core does not deserialise the frame again.  Panics on a device failure.
+    pub fn sanitize_view(&self, signer: Option<&Signer>, wire: &[u8], gc_round: u64,
+                         vote_target: Option<&[u8; 72]>) -> (Verdict, Option<[u8; 64]>, MsgView, Vec<u8>) {
+        let mut v = Verdict { code: 0, digest: [0u8; 32], kind: 3 };
+        let mut sig = [0u8; 64];
+        let mut voted: i32 = 0;
+        let mut view: MsgView = unsafe { std::mem::zeroed() };
+        let cap = unsafe { ffi::nwc_msg_view_body_bound(wire.len() as u64, 1) };
+        let mut body = vec![0u8; cap as usize];
+        let mut used: u64 = 0;
+        let rc = unsafe {
+            ffi::nwc_sanitizer_sanitize_view(self.h, signer.map_or(std::ptr::null_mut(), |s| s.h), wire.as_ptr(), wire.len(),
+                                             gc_round, vote_target.map_or(std::ptr::null(), |t| t.as_ptr()),
+                                             v.digest.as_mut_ptr(), &mut v.kind, sig.as_mut_ptr(), &mut voted,
+                                             &mut view as *mut MsgView as *mut std::ffi::c_void, body.as_mut_ptr(), cap, &mut used)
+        };
+        check(rc);
+        v.code = rc as u32;
+        body.truncate(used as usize);
+        (v, if voted != 0 { Some(sig) } else { None }, view, body)
+    }
+
+    /// Views delivered by a group flight / by the one-message fallback.
+    pub fn view_stats(&self) -> (u64, u64) {
+        let (mut in_flight, mut alone) = (0u64, 0u64);
+        check(unsafe { ffi::nwc_sanitizer_view_stats(self.h, &mut in_flight, &mut alone) });
+        (in_flight, alone)
+    }
+
     /// Votes signed inside a group flight / by the one-message fallback.
     pub fn vote_stats(&self) -> (u64, u64) {
         let (mut in_flight, mut alone) = (0u64, 0u64);
